@@ -9,7 +9,11 @@ backward + RCCL gradient all-reduce + fused SGD-momentum) on a synthetic VOC-sha
 images/GPU already resident in HBM.  Weak scaling: every rank keeps batch 32 (each replica is
 exactly the reference computation, local BatchNorm; SURVEY.md 8e option A).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs of the last step when `--dump-outputs DIR` is given, and the line (metric, value, unit, ms_per_step, dtype, config).
+`--full` adds everything else the benchmark measures, after the timed region:
+  sclk_mhz, board -- shader clock, board power and temperatures sampled over the timed region
+  comm         -- N > 1 / --dp-world1: the gradient all-reduce alone, the step without collectives, the overlap
   roofline     -- the DOMINANT device kernel of the step (largest summed duration; the raster-run
                   halo implicit-GEMM kernel that serves conv forward and dgrad), HIP-event timed
                   right after the timed region on the launch stream: algorithmic FLOPs per launch / average
@@ -20,7 +24,7 @@ Prints ONE JSON line (rank 0).  Extra objects:
                   kernel (fwd + dgrad + wgrad, all layers).
   cpu_baseline -- the CPU oracle (PyTorch-CPU restatement of the reference graph; TF 1.13 cannot
                   run here) timed on this box's host cores on a bounded sample (N=1 only).
-After the headline fields are final (N = 1, default configuration; `--no-extras` skips them):
+After the headline fields are final (--full, N = 1, default configuration; `--no-extras` skips them):
   sustained    -- the same step for >= 250 steps (~2 s) between two synchronisations
   inference    -- SSD300.test_one_image latency per engine (f32 = the test-mode default, f32x3, bf16), CPU oracle beside it
   configs      -- compact records of BASELINE.json's configurations 3-5 (yolov3, fcos, centernet, retinanet), one child run each
@@ -38,6 +42,8 @@ sys.path.insert(0, ROOT)
 
 MFMA_PEAK_BF16 = 2.5e15        # dense, /opt/skills/guides/MI355X_MICROARCH.md
 MFMA_PEAK_F32 = 157.3e12
+DUMP_SAMPLE = 1 << 15          # --dump-outputs: elements kept of a larger tensor (a fixed sample, seeded by the tensor's name)
+DUMP_LIMIT = 64 << 20          # --dump-outputs: bytes at most, all files together
 
 
 def synthetic_batch(batch, seed, device):
@@ -54,6 +60,37 @@ def synthetic_batch(batch, seed, device):
         cls = torch.randint(0, 20, (n,), generator=g).float()
         gt[i, :n] = torch.stack([yc, xc, h, w, cls], 1)
     return images.to(device), gt.to(device)
+
+
+def dump_outputs(model, loss, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files in `out_dir` -- `loss` (what train_step returned),
+    `loss_parts` (the per-image loss terms, where the class keeps them), `param.<name>` (every variable and moving statistic after the step's update, in
+    export_params() order and shape) and `grad.<name>` (the step's gradient of every variable, same shape).  A tensor of more than DUMP_SAMPLE elements is
+    reduced to DUMP_SAMPLE of them, at indices drawn by a generator seeded with the crc32 of its name: the same indices in every run and for the
+    parameter and its gradient, so two builds of the project compare output for output."""
+    import zlib
+    import numpy as np
+    arrays = {'loss': torch.as_tensor(loss.item() if hasattr(loss, 'item') else loss, dtype=torch.float32).reshape(1)}
+    if isinstance(getattr(model, 'loss_parts', None), torch.Tensor):
+        arrays['loss_parts'] = model.loss_parts
+    src = model._twin if getattr(model, '_twin', None) is not None else model          # mid-warm-up the live step runs on the twin
+    for k, v in model.export_params().items():
+        arrays['param.' + k] = v
+        if k in src.pinfo:
+            arrays['grad.' + k] = src.get_param(k, src.G)
+    os.makedirs(out_dir, exist_ok=True)
+    total, picks = 0, {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            key = name.split('.', 1)[-1]
+            if key not in picks:
+                picks[key] = np.sort(np.random.default_rng(zlib.crc32(key.encode())).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[picks[key]]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f'--dump-outputs: more than {DUMP_LIMIT >> 20} MB'
+        np.save(os.path.join(out_dir, name.replace(os.sep, '_') + '.npy'), a)
 
 
 class ConvTimer:
@@ -272,9 +309,15 @@ def main():
                          'yolov3 = config 4 (416x416, 8 / GPU); fcos | centernet = config 5 (512x512, 16 / GPU) -- bench_configs.py')
     ap.add_argument('--batch', type=int, default=None, help='images per GPU (default: the configuration\'s)')
     ap.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'f32x3'], help='engine (default: the one the model class defaults to in training mode: bf16 for ssd300 / fcos / centernet, f32x3 -- f32 tensors, ODTK_F32X3 convolution descriptors -- for retinanet and, since round 6, yolov3)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-conv-events', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='N = 1, ssd300: skip what follows the headline measurement (sustained run, live PMC traffic passes, '
+    ap.add_argument('--full', action='store_true', help='measure more than the headline, after the timed region: the roofline pass (HIP events per conv launch), '
+                                                        'clock / board samples, N > 1 communication figures, the CPU baseline and, N = 1 ssd300, the extras '
+                                                        '(sustained, live PMC traffic, inference, epoch, configs); the --no-* switches below trim it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed (loss, loss terms, updated parameters, gradients; '
+                         f'tensors above {DUMP_SAMPLE} elements as a fixed seeded sample) to DIR/<name>.npy, float32')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: no CPU baseline')
+    ap.add_argument('--no-conv-events', action='store_true', help='--full: no roofline pass')
+    ap.add_argument('--no-extras', action='store_true', help='--full, N = 1, ssd300: skip what follows the headline measurement (sustained run, live PMC traffic passes, '
                                                              'test_one_image latency, the compact records of configurations 3-5)')
     ap.add_argument('--eager', action='store_true', help='no HIP-graph replay in the timed region (the default at N = 1 since round 3)')
     ap.add_argument('--launch-list', action='store_true', help="N = 1: use_graph='list' -- the step's C-ABI calls replayed from a recorded list of pre-bound argument "
@@ -286,7 +329,7 @@ def main():
     ap.add_argument('--no-tail-stream', action='store_true', help='A/B: heads after the extra layers on one stream (round-1 order)')
     ap.add_argument('--no-fuse-pool', action='store_true', help='A/B: conv1_2 and pool1 as two launches (the un-pooled map is stored and read back)')
     ap.add_argument('--sync-bn', action='store_true', help='N > 1: batch-norm statistics over all replicas (SURVEY 8e option B; eager launches)')
-    ap.add_argument('--conv-table', default=None, help='write the per-layer conv launch table (eager roofline pass) to this file')
+    ap.add_argument('--conv-table', default=None, help='--full: write the per-layer conv launch table (eager roofline pass) to this file')
     ap.add_argument('--kernel-dbg', type=int, default=0, help='A/B: odtk_debug_set(2, bits) dispatch switches of csrc/conv_v3.hip (bits >= 1<<26 only)')
     ap.add_argument('--debug-set', default='', help="A/B: comma list of KEY:VALUE for odtk_debug_set (keys that leave results intact: 3, 4, 5, 6, 7)")
     ap.add_argument('--model-cfg', default='', help="A/B: comma list of KEY=VALUE config overrides of the model class (e.g. heads_first=1)")
@@ -303,6 +346,10 @@ def main():
                     help='exercise ONLY the launcher / rendezvous / timing / one-JSON-line skeleton with a dummy all-reduce step '
                          '(gloo when there is no GPU); prints metric "launch-check", never a measurement')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.conv_table and not (args.full and not args.no_conv_events):
+        ap.error('--conv-table needs the roofline pass: --full without --no-conv-events')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:], need_gpus=not args.launch_check))
@@ -354,8 +401,10 @@ def main():
     images, gt = synthetic_batch(B, 1000 + rank, dev)
     model.set_batch(images, gt)
 
+    conv_events = args.full and not args.no_conv_events
     timer = ConvTimer(ops)
-    timer.install()
+    if conv_events:
+        timer.install()
 
     def barrier():
         torch.cuda.synchronize()
@@ -380,18 +429,22 @@ def main():
     gc.collect()
     gc.disable()               # a generation-2 collection in the launching thread is a 10-30 ms host stall; with eager launches
     barrier()                  # (the HIP-event pass below) the GPU runs dry behind it and the stall lands in some kernel's events
-    clock = ClockSampler(local_rank)
-    clock.start()
+    clock = ClockSampler(local_rank) if args.full else None
+    if clock is not None:
+        clock.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = model.train_step(lr)
     barrier()
     dt = time.perf_counter() - t0
-    clock.stop()
+    if clock is not None:
+        clock.stop()
     final_loss_t = loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)
     # roofline pass: the SAME step launched eagerly with HIP events around every conv launch on the launch
     # stream (graph replay cannot carry per-kernel events; the kernels and their durations are identical)
-    if not args.no_conv_events:
+    if conv_events:
         # ONE stream for this pass: the head stream, the tail filter-gradient stream, the optional filter-gradient stream and the side-stream front / tail
         # of the step are all switched off, so every conv kernel is timed with the chip to itself and the per-kernel table is not deflated by kernels
         # that share CUs (round 3 left the head / tail streams on: `conv_ms_per_step` exceeded `ms_per_step`).  The timed region above is untouched.
@@ -418,7 +471,8 @@ def main():
         tmax = torch.tensor([dt], device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-        comm = comm_metrics(model, args, lr, barrier, dt / args.steps * 1e3, dev)
+        if args.full:
+            comm = comm_metrics(model, args, lr, barrier, dt / args.steps * 1e3, dev)
     final_loss = float(loss.item())
 
     if rank == 0:
@@ -446,20 +500,21 @@ def main():
                                               'every conv launch has the chip to itself; HIP events per conv launch on the launch stream; plain per-launch mean '
                                               'without the first eager step; *_trimmed additionally drops the slowest sample of every launch)')
             out['roofline']['single_stream_ms_per_step'] = round(single_stream_ms, 3)   # incl. the event records: an upper bound of conv_ms_per_step
-        out['sclk_mhz'] = clock.summary()
-        out['board'] = clock.board()
+        if clock is not None:
+            out['sclk_mhz'] = clock.summary()
+            out['board'] = clock.board()
         if comm is not None:
             out['comm'] = comm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
-        if world == 1 and not args.no_extras and not args.dp_world1:
+        if args.full and world == 1 and not args.no_extras and not args.dp_world1:
             # Everything below runs AFTER the headline measurement and outside its timed region; the headline fields above are final.
             t_extras = time.perf_counter()
             try:
                 out['sustained'] = sustained_run(model, lr, B, local_rank)
             except Exception as e:                                       # noqa: BLE001
                 out['sustained'] = {'error': f'{type(e).__name__}: {e}'}
-            if 'roofline' in out and not args.no_conv_events:
+            if 'roofline' in out and conv_events:
                 out['roofline'].update(live_pmc_traffic(out['roofline']))
             try:
                 out['inference'] = inference_bench(dev, with_cpu=not args.no_cpu_baseline)
@@ -656,7 +711,7 @@ def inference_bench(dev, with_cpu=True, reps=20):
 
 
 def configs_bench(budget_s=120.0, pmc=True):
-    """BASELINE.json's configurations 3-5, one child `python bench.py --config <name> --steps 10 --warmup 3 --no-cpu-baseline` each (its own process: a failure there
+    """BASELINE.json's configurations 3-5, one child `python bench.py --config <name> --steps 10 --warmup 3 --full --no-cpu-baseline` each (its own process: a failure there
     cannot touch the headline line), reduced to a compact record: images/s, ms/step, engine, dominant kernel and its fraction of the engine's MFMA peak, the conv
     family's fraction.  Stops starting children when the time budget of the default run is spent."""
     import subprocess
@@ -675,7 +730,7 @@ def configs_bench(budget_s=120.0, pmc=True):
             res[name] = {'skipped': 'time budget of the default run spent'}
             continue
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--config', name.split('_')[0], '--steps', '10', '--warmup', '3', '--no-cpu-baseline'] + extra,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--config', name.split('_')[0], '--steps', '10', '--warmup', '3', '--full', '--no-cpu-baseline'] + extra,
                                stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=min(left, 90))
             line = [ln for ln in r.stdout.decode(errors='replace').splitlines() if ln.startswith('{')]
             if r.returncode != 0 or not line:
@@ -729,9 +784,11 @@ def bench_other(args, world, rank, local_rank):
     if world > 1:
         model.attach_data_parallel(bucket_mb=args.bucket_mb, grad_dtype=args.grad_dtype)
     model.set_batch(r['images'], r['gt'])
+    conv_events = args.full and not args.no_conv_events
     alg = {id(d): (cin, cout) for d, cin, cout, _ in BC.conv_layers(name, model)}
     timer = ConvTimer(ops, alg)
-    timer.install()
+    if conv_events:
+        timer.install()
 
     def barrier():
         torch.cuda.synchronize()
@@ -751,8 +808,10 @@ def bench_other(args, world, rank, local_rank):
     barrier()
     dt = time.perf_counter() - t0
     final_loss = float(loss.item() if hasattr(loss, 'item') else loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)
     ev_steps = min(args.steps, 3) + 1
-    if not args.no_conv_events:
+    if conv_events:
         timer.enabled = True
         for _ in range(ev_steps):
             model.train_step(lr)
@@ -786,7 +845,7 @@ def bench_other(args, world, rank, local_rank):
             rf['peak_note'] = ('dense bf16 MFMA' if args.dtype == 'bf16' else 'dense bf16 MFMA / 3 (three bf16 products per f32 product)' if args.dtype == 'f32x3'
                                else 'f32-input MFMA = the f32 vector rate (MI355X_MICROARCH.md)')
             out['roofline'] = rf
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_other(name)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -45,6 +45,54 @@ def test_mismatched_world_size_is_an_error_message_not_an_assert():
     assert r.returncode != 0 and 'WORLD_SIZE=4' in r.stderr and 'Traceback' not in r.stderr
 
 
+def test_dump_outputs_of_a_training_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed: the loss, the loss terms, every variable after the update and its gradient,
+    float32, large tensors as a sample whose indices depend only on the tensor's name (the same in every run, for a parameter and its gradient alike).
+    Here on one SSD300 step through tests/mock_ops.py's launches."""
+    import zlib
+    import numpy as np
+    import torch
+    import bench
+    import mock_ops
+    import odtk
+    from oracle import ssd300_ref as R
+    torch.set_num_threads(8)
+    cfg = {'mode': 'train', 'data_format': 'channels_last', 'num_classes': 20, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'batch_size': 2,
+           'nms_score_threshold': 0.5, 'nms_max_boxes': 20, 'nms_iou_threshold': 0.5, 'pretraining_weight': '', 'verbose': False,
+           'compute_dtype': 'f32', 'seed': 0, 'use_graph': False, 'device': 'cpu'}
+    imgs, gt = R.synthetic_batch(2, 31)
+    with mock_ops.installed():
+        m = odtk.SSD300(cfg, {'data_shape': [300, 300, 3], 'num_train': 2, 'num_val': 0, 'train_generator': [], 'val_generator': None})
+        m.set_batch(imgs, gt)
+        loss = m.train_step(0.01)
+        bench.dump_outputs(m, loss, str(tmp_path / 'a'))
+        bench.dump_outputs(m, loss, str(tmp_path / 'b'))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b'))
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= bench.DUMP_LIMIT
+    load = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    for f in files:
+        assert load[f[:-4]].dtype == np.float32 and np.array_equal(load[f[:-4]], np.load(tmp_path / 'b' / f)), f
+    assert load['loss'].tolist() == [np.float32(float(loss))]
+    assert np.array_equal(load['loss_parts'], m.loss_parts.numpy())
+    params = m.export_params()
+    assert {k for k in load if k.startswith('param.')} == {'param.' + k for k in params}
+    assert {k for k in load if k.startswith('grad.')} == {'grad.' + k for k in m.pinfo}
+    sampled = 0
+    for k, v in params.items():
+        p = v.numpy().reshape(-1)
+        g = m.get_param(k, m.G).numpy().reshape(-1) if k in m.pinfo else None
+        if p.size <= bench.DUMP_SAMPLE:
+            assert np.array_equal(load['param.' + k], v.numpy()), k
+            assert g is None or np.array_equal(load['grad.' + k].reshape(-1), g), k
+        else:
+            sampled += 1
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(p.size, bench.DUMP_SAMPLE, replace=False))
+            assert np.array_equal(load['param.' + k], p[idx]), k
+            assert np.array_equal(load['grad.' + k], g[idx]), k                 # the gradient at the same indices
+    assert sampled > 0
+
+
 def test_real_run_without_gpus_fails_loudly():
     r = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '1'])
     assert r.returncode == 2 and 'GPU(s) visible' in r.stderr

@@ -306,7 +306,7 @@ def test_rccl_world1_data_parallel_training_step(dev, grad_dtype, launch):
     the filter-gradient stream while the backward pass keeps the head / filter-gradient streams of the single-device step (eager launches, the default since
     round 4); `--graph`: one backward HIP graph per bucket captured thread-locally beside RCCL's watchdog, the all-reduces between the replays; (bf16:
     narrowed / widened buckets) -- and the loss stays that of the single-device step (the sum over one rank is the identity)."""
-    base = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-conv-events', '--no-extras']
+    base = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-conv-events', '--no-extras']
     dp = _bench_json(base + ['--dp-world1', '--grad-dtype', grad_dtype] + (['--graph'] if launch == 'graph' else []))
     one = _bench_json(base)
     assert dp['comm']['backend'] == 'nccl' and dp['comm']['world_size'] == 1 and dp['comm']['buckets'] >= 3
@@ -322,7 +322,7 @@ def test_rccl_world1_data_parallel_step_is_bit_identical_in_deterministic_mode(d
     """The same pair of bench.py runs (plain | --dp-world1: RCCL process group of one rank, gradient buckets all-reduced by torch.distributed from the
     filter-gradient stream) with odtk_debug_set(5, 1): since round 5 the whole step is reproducible bit for bit in that mode, so the loss after
     seven optimizer steps at batch 32 is not "within 3 %" (the test above: float atomics) but EQUAL."""
-    base = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-conv-events', '--no-extras', '--debug-set', '5:1']
+    base = ['--gpus', '1', '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-conv-events', '--no-extras', '--debug-set', '5:1']
     dp = _bench_json(base + ['--dp-world1'])
     one = _bench_json(base)
     assert dp['comm']['backend'] == 'nccl' and dp['comm']['buckets'] >= 3 and dp['config']['launch'] == 'eager'

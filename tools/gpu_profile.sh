@@ -3,7 +3,7 @@
 #   bash tools/gpu_profile.sh <tag>      -> gpurun_out/<tag>/{trace.md, pmc.md, pmc.json, bench.log}
 set -u
 TAG=${1:-prof}; R=$(pwd); O=$R/gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
-timeout 600 python bench.py > $O/bench.log 2>&1
+timeout 600 python bench.py --full > $O/bench.log 2>&1
 BCMD="python bench.py --steps 4 --warmup 3 --no-cpu-baseline --no-conv-events --eager --no-extras"
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -- $BCMD > $O/trace.log 2>&1
 python tools/summarize_trace_csv.py $O/trace 7 > $O/trace.md
