@@ -461,6 +461,18 @@ int odtk_retina_loss(const float* pconf, const float* pbox, int N, int A, int C,
                      const float* hw, const float* gt, int P, const int* ngt, const int* best,
                      const unsigned char* status, const int* rgindex, const int* counts, float alpha,
                      float gamma, float grad_scale, float* loss_parts, float* dconf, float* dbox, void* stream);
+/* RetinaNet classification pre-training head (RetinaNet.py:120-135): logits = reduce_mean over H, W of the last residual unit,
+ * sparse softmax cross-entropy, arg-max.  x: rows [N * HW][ldx] (dtype ODTK_F32 / ODTK_BF16, image n = rows n * HW ..), C <= ldx, C <= 1024.
+ *   logits [N][C] f32 = (sum of the HW rows in row order, f32) / HW;  pred [N] int32 = first index of the maximum logit (TF's tie rule).
+ *   With labels (int32 [N], in [0, C): the caller checks; an out-of-range label gives a NaN loss and no out-of-bounds read):
+ *   loss [N] = log-sum-exp - logit[label] (per image: the caller takes the batch mean), correct [N] = (pred == label) as 0 / 1 f32, and,
+ *   if dlogits is not NULL, dlogits [N][C] = (softmax - onehot(label)) * grad_scale (grad_scale = 1 / batch for the batch mean).
+ *   Without labels (inference) loss, correct and dlogits must be NULL.  One workgroup per image, no atomics: bit-identical run to run.
+ * odtk_gap_softmax_ce_bwd: dx[n * HW + hw][c] = dlogits[n][c] / HW (accumulate: +=) in rows of `dtype` with pitch lddx; pad columns
+ *   [C, lddx) are written as zero. */
+int odtk_gap_softmax_ce_fwd(const void* x, int dtype, int N, int HW, int C, int ldx, const int* labels, float grad_scale,
+                            float* logits, float* loss, int* pred, float* correct, float* dlogits, void* stream);
+int odtk_gap_softmax_ce_bwd(const float* dlogits, int N, int HW, int C, void* dx, int dtype, int lddx, int accumulate, void* stream);
 /* RetinaNet inference branch up to the per-class NMS loop (RetinaNet.py:224-238): softmax, background-arg-max mask,
  * box decode; outputs as odtk_ssd_decode (conf [A][C-1], boxes [A][4] y1,x1,y2,x2, keep [A], cand [A][C-1]). */
 int odtk_retina_decode(const float* pconf, const float* pbox, int A, int C, const float* yx, const float* hw,

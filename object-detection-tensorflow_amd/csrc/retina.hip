@@ -375,6 +375,83 @@ __global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_kernel(const RLoss
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Classification pre-training head (RetinaNet.py:120-135): global average pool of the last residual unit, sparse softmax
+// cross-entropy, first-index arg-max.  One workgroup per image; thread t owns channels t, t + 256, ... and sums its HW rows in row
+// order; the max / arg-max and the sum of exponentials go through a 64-lane butterfly whose lane-0 result (a fixed order) is taken,
+// then the four waves in wave order: the outputs are bit-identical from run to run (no atomics).
+constexpr int GAP_THREADS = 256, GAP_MAXC = 1024;
+
+template <typename T>
+__global__ void __launch_bounds__(GAP_THREADS) gap_softmax_ce_fwd_kernel(
+    const T* __restrict__ x, int HW, int C, int ld, const int* __restrict__ labels, float grad_scale, float* __restrict__ logits,
+    float* __restrict__ loss, int* __restrict__ pred, float* __restrict__ correct, float* __restrict__ dlogits) {
+    __shared__ float s_z[GAP_MAXC];
+    __shared__ float s_v[GAP_THREADS / 64];
+    __shared__ int s_i[GAP_THREADS / 64];
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* xn = x + (size_t)n * HW * ld;
+    float m = -INFINITY; int mi = 0x7fffffff;
+    for (int c = tid; c < C; c += GAP_THREADS) {
+        float s = 0.f;
+        for (int r = 0; r < HW; ++r) s += elem<T>::load(xn[(size_t)r * ld + c]);
+        const float z = s / (float)HW;                                  // reduce_mean: sum, then one division
+        s_z[c] = z;
+        logits[(size_t)n * C + c] = z;
+        if (z > m || mi == 0x7fffffff) { m = z; mi = c; }             // ascending c: strict > keeps the first maximum
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o); const int i2 = __shfl_xor(mi, o);
+        if (m2 > m || (m2 == m && i2 < mi)) { m = m2; mi = i2; }
+    }
+    if (lane == 0) { s_v[wave] = m; s_i[wave] = mi; }
+    __syncthreads();
+    float bm = s_v[0]; int bi = s_i[0];
+    for (int w = 1; w < GAP_THREADS / 64; ++w)
+        if (s_v[w] > bm || (s_v[w] == bm && s_i[w] < bi)) { bm = s_v[w]; bi = s_i[w]; }
+    if (bi >= C) bi = 0;                                               // every logit NaN: no maximum
+    __syncthreads();
+    float e = 0.f;
+    for (int c = tid; c < C; c += GAP_THREADS) e += expf(s_z[c] - bm);
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    if (lane == 0) s_v[wave] = e;
+    __syncthreads();
+    float se = s_v[0];
+    for (int w = 1; w < GAP_THREADS / 64; ++w) se += s_v[w];
+    if (tid == 0) pred[n] = bi;
+    if (!labels) return;
+    const int lab = labels[n];
+    const bool ok = lab >= 0 && lab < C;                               // the host rejects others; no read outside the row here
+    if (tid == 0) {
+        loss[n] = ok ? logf(se) - (s_z[lab] - bm) : NAN;               // lse - logit[label], both shifted by the max
+        correct[n] = bi == lab ? 1.f : 0.f;
+    }
+    if (dlogits) {
+        const float inv = 1.f / se;
+        for (int c = tid; c < C; c += GAP_THREADS)
+            dlogits[(size_t)n * C + c] = (expf(s_z[c] - bm) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+    }
+}
+
+// dx[n * HW + hw][c] (+)= dlogits[n][c] / HW for c < C; pad columns [C, ld) are written as zero
+template <typename T>
+__global__ void __launch_bounds__(256) gap_softmax_ce_bwd_kernel(const float* __restrict__ dlogits, int HW, int C, int ld, long long total,
+                                                                 T* __restrict__ dx, int accumulate) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const long long r = i / ld;
+        const int c = (int)(i - r * ld);
+        const int n = (int)(r / HW);
+        float v = 0.f;
+        if (c < C) {
+            v = dlogits[(size_t)n * C + c] / (float)HW;
+            if (accumulate) v += elem<T>::load(dx[i]);
+        }
+        dx[i] = elem<T>::store(v);
+    }
+}
+
 }  // namespace
 }  // namespace odtk
 
@@ -441,6 +518,41 @@ extern "C" int odtk_retina_loss(const float* pconf, const float* pbox, int N, in
     a.alpha = alpha; a.gamma = gamma; a.grad_scale = grad_scale; a.loss_parts = loss_parts; a.dconf = dconf; a.dbox = dbox;
     hipLaunchKernelGGL(retina_loss_kernel, dim3(nparts, N), dim3(RL_THREADS), 0, st, a);
     hipLaunchKernelGGL(retina_best_rows_kernel, dim3(N), dim3(RL_MAX_GT), 0, st, a, nparts);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+
+extern "C" int odtk_gap_softmax_ce_fwd(const void* x, int dtype, int N, int HW, int C, int ldx, const int* labels, float grad_scale,
+                                       float* logits, float* loss, int* pred, float* correct, float* dlogits, void* stream) {
+    ODTK_REQUIRE(x && logits && pred, "gap_softmax_ce_fwd: null pointer");
+    ODTK_REQUIRE(labels ? (loss && correct) : (!loss && !correct && !dlogits),
+                 "gap_softmax_ce_fwd: loss / correct (and dlogits, optional) come with labels, and only with them");
+    ODTK_REQUIRE(N > 0 && HW > 0 && C > 0 && C <= GAP_MAXC && ldx >= C, "gap_softmax_ce_fwd: N=%d HW=%d C=%d ld=%d unsupported (C <= %d)",
+                 N, HW, C, ldx, GAP_MAXC);
+    ODTK_REQUIRE(dtype == ODTK_F32 || dtype == ODTK_BF16, "gap_softmax_ce_fwd: dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ODTK_F32)
+        hipLaunchKernelGGL(gap_softmax_ce_fwd_kernel<float>, dim3(N), dim3(GAP_THREADS), 0, st, (const float*)x, HW, C, ldx, labels, grad_scale,
+                           logits, loss, pred, correct, dlogits);
+    else
+        hipLaunchKernelGGL(gap_softmax_ce_fwd_kernel<bf16_t>, dim3(N), dim3(GAP_THREADS), 0, st, (const bf16_t*)x, HW, C, ldx, labels, grad_scale,
+                           logits, loss, pred, correct, dlogits);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+
+extern "C" int odtk_gap_softmax_ce_bwd(const float* dlogits, int N, int HW, int C, void* dx, int dtype, int lddx, int accumulate, void* stream) {
+    ODTK_REQUIRE(dlogits && dx, "gap_softmax_ce_bwd: null pointer");
+    ODTK_REQUIRE(N > 0 && HW > 0 && C > 0 && C <= GAP_MAXC && lddx >= C, "gap_softmax_ce_bwd: N=%d HW=%d C=%d ld=%d unsupported (C <= %d)",
+                 N, HW, C, lddx, GAP_MAXC);
+    ODTK_REQUIRE(dtype == ODTK_F32 || dtype == ODTK_BF16, "gap_softmax_ce_bwd: dtype %d", dtype);
+    const long long total = (long long)N * HW * lddx;
+    const int grid = (int)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ODTK_F32)
+        hipLaunchKernelGGL(gap_softmax_ce_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, dlogits, HW, C, lddx, total, (float*)dx, accumulate);
+    else
+        hipLaunchKernelGGL(gap_softmax_ce_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, dlogits, HW, C, lddx, total, (bf16_t*)dx, accumulate);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }

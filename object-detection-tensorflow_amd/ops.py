@@ -482,6 +482,18 @@ def retina_decode(pconf, pbox, yx, hw, thr):
     return conf, boxes, keep, cand
 
 
+def gap_softmax_ce_fwd(x, ldx, N, HW, C_, labels, grad_scale, logits, loss, pred, correct, dlogits):
+    """RetinaNet pre-training head (include/odtk.h): rows x [N * HW][ldx] -> logits [N][C] f32, pred [N] int32; with labels (int32 [N]) also
+    loss [N], correct [N] and, if dlogits is given, dlogits [N][C] = (softmax - onehot) * grad_scale.  labels=None: inference (pred only)."""
+    call("odtk_gap_softmax_ce_fwd", _p(x), dt_of(x), int(N), int(HW), int(C_), int(ldx), _p(labels), float(grad_scale), _p(logits), _p(loss), _p(pred),
+         _p(correct), _p(dlogits), _stream())
+
+
+def gap_softmax_ce_bwd(dlogits, N, HW, C_, dx, lddx, accumulate=False):
+    """dx[n * HW + hw][:C] (+)= dlogits[n] / HW, pad columns of dx zeroed"""
+    call("odtk_gap_softmax_ce_bwd", _p(dlogits), int(N), int(HW), int(C_), _p(dx), dt_of(dx), int(lddx), int(accumulate), _stream())
+
+
 # ---------------------------------------------------------------------------------------------------------
 # CenterNet / FCOS box side (include/odtk.h; csrc/dense_heads.hip)
 # ---------------------------------------------------------------------------------------------------------

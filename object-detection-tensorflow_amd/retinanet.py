@@ -9,7 +9,11 @@ Reference: /root/reference/RetinaNet.py -- the DETECTION graph (`is_pretraining:
   * loss, optimizer ...................... :172-217  (odtk_retina_match / odtk_retina_loss; Momentum 0.9; L2 over all variables)
   * inference ............................ :218-256  (heads.retina_detect)
   * train / test / checkpoints ........... :488-535
-The classification pre-training graph (`is_pretraining: True`, :120-135) is not built: NotImplementedError.
+The classification pre-training graph (`is_pretraining: True`, :61-99, :120-135, :476-531, :548-551) is built behind the same class:
+  * the backbone alone (l0 .. l64), the LAST unit's sum (no batch norm / ReLU after it) -> global average pool -> softmax cross-entropy
+    (odtk_gap_softmax_ce_fwd / _bwd): 4 * FILTERS[-1] = 224 logits, no dense layer, config['num_classes'] plays no part; labels int [N] in [0, 224)
+  * train_one_epoch -> (mean loss, mean accuracy); test_one_image -> pred int64 [1]; save_weight -> the 260 trainables of 'feature_extractor'
+  * the moving statistics are NEVER updated (the pre-training train_op has no UPDATE_OPS dependency, :134): they stay 0 / 1, test mode uses them
 Same conventions as yolov3.py: layers l0 .. l121 in creation order (layer k = conv k + batch norm k; l0 is conv -> BN -> ReLU, every
 other layer BN -> ReLU -> conv with a LIVE bias gradient), one flat f32 parameter buffer, NHWC rows with zero-filled pad columns for
 the 7 / 14 / 28-channel maps.  A batch norm whose input feeds several consumers accumulates its dx through a scratch + odtk_add2d.
@@ -89,8 +93,7 @@ class RetinaNet:
         assert len(config['data_shape']) == 3
         assert config['mode'] in ['train', 'test']
         assert config['data_format'] in ['channels_first', 'channels_last']
-        if config.get('is_pretraining'):
-            raise NotImplementedError('the classification pre-training graph (RetinaNet.py:120-135) is not built; is_pretraining must be False')
+        self.is_pretraining = bool(config.get('is_pretraining'))
         assert config['is_bottleneck'], 'only the bottleneck units of testretinanet.py are built'
         self.config = config
         self.data_provider = data_provider
@@ -137,8 +140,15 @@ class RetinaNet:
         if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
             torch.cuda.set_device(self.dev)
         self.specs = layer_specs(self.block_list, config['init_conv_filters'], self.num_classes, self.num_anchors)
+        if self.is_pretraining:                     # the backbone alone: stem + units (RetinaNet.py:120-122)
+            self.specs = self.specs[: 1 + 4 * sum(self.block_list)]
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
+        if self.is_pretraining:                     # the reference swaps its class surface the same way (:61-68)
+            self.save_weight = self._save_pretraining_weight
+            self.load_weight = self._load_pretraining_model_weight
+            self.train_one_epoch = self._train_pretraining_epoch
+            self.test_one_image = self._test_one_pretraining_image
 
     # ------------------------------------------------------------------ parameters
     def param_layout(self):
@@ -295,6 +305,8 @@ class RetinaNet:
                 branch = bnconv(bnconv(bnconv(x)))
                 x = add(branch, bnconv(x))
             feats.append(x)
+        if self.is_pretraining:
+            return self._build_pretraining(x, it)
         f1, f2, f3 = feats[-3:]
         p5 = bnconv(f3)
         total4 = resize_add(bnconv(f2), p5)
@@ -347,6 +359,9 @@ class RetinaNet:
                 _, c, target, off, width = op
                 self.bplan.append(op)
                 written.add(find(c.gid))
+            elif kind == 'gap':                         # the pre-training head is the gradient source: dx lands in the last sum's buffer
+                self.bplan.append(op)
+                written.add(find(op[1].gid))
             elif kind == 'bnconv':
                 _, name, x, y, out = op
                 assert find(out.gid) in written, name
@@ -388,6 +403,13 @@ class RetinaNet:
     # ------------------------------------------------------------------ forward / loss / backward
     def _bn_relu(self, name, x, y, training):
         sm, si = self.bnsave[name]
+        if self.is_pretraining and training:
+            # deliberate: the pre-training train_op is optimizer.minimize() WITHOUT the UPDATE_OPS dependency of the detection graph (RetinaNet.py:134
+            # against :221-222), so under TF the moving statistics stay 0 / 1 for the whole pre-training and test mode normalises with them.
+            # odtk_bn_fwd always updates the statistics it is handed: it gets a throwaway scratch
+            ops.bn_fwd(x.t, x.M, x.C, x.ld, self.param(name + '.gamma'), self.param(name + '.beta'), self.stat_scratch[: x.C],
+                       self.stat_scratch[x.C: 2 * x.C], sm, si, training, 1, y.t, y.ld, x.M, 0, self.ws)
+            return
         ops.bn_fwd(x.t, x.M, x.C, x.ld, self.param(name + '.gamma'), self.param(name + '.beta'), self.stat(name + '.mmean'),
                    self.stat(name + '.mvar'), sm, si, training, 1, y.t, y.ld, x.M, 0, self.ws)
 
@@ -410,6 +432,8 @@ class RetinaNet:
                 _, c, target, off, width = op
                 K = self.num_anchors * width
                 ops.rows_to_f32(c.t, c.ld, target[0, off:], K, c.H * c.W, target.shape[1] * width, c.M, K)
+            elif kind == 'gap':
+                self._gap_head(training)
             elif kind == 'stem':
                 _, name, src, z, y = op
                 ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), z.t, False)
@@ -436,6 +460,9 @@ class RetinaNet:
                 d = self.dconf if target is self.pconf else self.dbox
                 K = self.num_anchors * width
                 ops.rows_from_f32(d[0, off:], K, c.H * c.W, d.shape[1] * width, self.grad_of(c), c.ld, c.M, K)
+            elif kind == 'gap':
+                f = op[1]
+                ops.gap_softmax_ce_bwd(self.dlogits, f.N, f.H * f.W, f.C, self.grad_of(f), f.ld, False)
             elif kind == 'bnconv':
                 _, name, x, y, out, acc = op
                 dz = self.grad_of(out)
@@ -467,6 +494,8 @@ class RetinaNet:
 
     # ------------------------------------------------------------------ public: training
     def set_batch(self, images, ground_truth):
+        if self.is_pretraining:                     # (images, labels)
+            return self._set_pretraining_batch(images, ground_truth)
         images = torch.as_tensor(images, dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)
@@ -479,6 +508,8 @@ class RetinaNet:
 
     def train_step(self, lr):
         """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
+        if self.is_pretraining:
+            return self._pretraining_step(lr)
         if self.dist is not None:
             self.dist.begin_step()
         self.G.zero_()
@@ -555,6 +586,8 @@ class RetinaNet:
         for tfname, ours in reference_variable_map(self.block_list).items():
             if backbone_only and int(ours[1:].split('.')[0]) >= nb:
                 continue
+            if ours in self.sinfo and not reader.has_tensor(tfname):
+                continue                                # a pre-training checkpoint holds no moving statistics (RetinaNet.py:548-551)
             v = torch.from_numpy(reader.get_tensor(tfname))
             if ours in self.sinfo:
                 self.stat(ours).copy_(v.to(self.dev))
@@ -624,10 +657,165 @@ class RetinaNet:
         print('load pretraining weight', path, 'successfully')
 
     def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
+        if self.is_pretraining:
+            raise NotImplementedError('data-parallel training of the classification pre-training graph is not built yet: run it on one device')
         from .dist import GradAllReducer
         self.dist = GradAllReducer(self, group, bucket_mb, grad_dtype, force_collectives, collective)
         self.loss_divisor_batch = self.batch_size * self.dist.world
         return self.dist
+
+    # ------------------------------------------------------------------ classification pre-training (is_pretraining: True)
+    def _build_pretraining(self, feat, it):
+        """the rest of _build for the pre-training graph (RetinaNet.py:120-135): the last unit's sum -> global average pool -> softmax
+        cross-entropy.  No pyramid, subnets or anchors."""
+        assert next(it, None) is None
+        N, dev, dt = self.batch_size, self.dev, self.tdt
+        self.feat = feat                              # C = 4 * FILTERS[-1] = 224 logits (no dense layer, :124-125)
+        self.plan.append(('gap', feat))
+        self.levels, self.shapes, self.num_anchor_boxes, self.anc = [], [], 0, None
+        # zero anchors: the detection loss buffers that _build_backward allocates come out empty
+        self.pconf = torch.zeros(N, 0, self.num_classes, device=dev)
+        self.pbox = torch.zeros(N, 0, 4, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.labels = torch.zeros(N, **i32)
+        self.logits = torch.zeros(N, feat.C, device=dev)
+        self.ce = torch.zeros(N, device=dev)
+        self.pred = torch.zeros(N, **i32)
+        self.correct = torch.zeros(N, device=dev)
+        self.dlogits = torch.zeros(N, feat.C, device=dev)
+        self.last_accuracy = torch.zeros((), device=dev)
+        self.stat_scratch = torch.zeros(2 * max(s[5] for s in self.specs), device=dev)     # the moving statistics odtk_bn_fwd updates (_bn_relu)
+        self.ws = torch.zeros(self._max_ws, dtype=torch.uint8, device=dev)
+        self.wt, entries = {}, []
+        for name, cin, cout, k, _, _, _ in self.specs[1:]:
+            d = self.desc[name]
+            kp = self.acts[name].ld
+            self.wt[name] = torch.zeros(d.C * k * k * kp, dtype=dt, device=dev)
+            entries.append((self._flat(name + '.w', self.P), self.wt[name], cout, k, k, d.C, kp))
+        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        if self.mode == 'train':
+            self._build_backward(N, 0, dt, dev)
+        self._refresh_operand_copies()
+
+    @property
+    def num_pretraining_classes(self):
+        return self.feat.C
+
+    def _gap_head(self, with_labels):
+        f = self.feat
+        if with_labels:
+            ops.gap_softmax_ce_fwd(f.t, f.ld, f.N, f.H * f.W, f.C, self.labels, 1.0 / self.loss_divisor_batch, self.logits, self.ce, self.pred,
+                                   self.correct, self.dlogits)
+        else:
+            ops.gap_softmax_ce_fwd(f.t, f.ld, f.N, f.H * f.W, f.C, None, 0., self.logits, None, self.pred, None, None)
+
+    def _set_pretraining_batch(self, images, labels):
+        images = torch.as_tensor(images, dtype=torch.float32)
+        if self.data_format == 'channels_first' and images.shape[1] == 3:
+            images = images.permute(0, 2, 3, 1)
+        assert tuple(images.shape) == tuple(self.images.shape), images.shape
+        lab = np.asarray(labels.detach().cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+        C = self.feat.C
+        if lab.shape[0] != self.batch_size or lab.dtype.kind not in 'iuf' or (lab.dtype.kind == 'f' and not np.array_equal(lab, np.trunc(lab))):
+            raise ValueError(f'labels: {self.batch_size} integer class ids expected, got {lab.dtype} {lab.shape}')
+        if lab.size and (lab.min() < 0 or lab.max() >= C):
+            # the pre-training logits are the {C} channels of the last unit (RetinaNet.py:124-126); TF's GPU kernel would give a NaN loss
+            raise ValueError(f'labels must lie in [0, {C}): got [{lab.min()}, {lab.max()}]')
+        self.images.copy_(images, non_blocking=True)
+        self.labels.copy_(torch.from_numpy(lab.astype(np.int32)), non_blocking=True)
+
+    def _pretraining_step(self, lr):
+        """RetinaNet.py:126-135: loss = mean CE + wd * sum l2 over l0 .. l64, Momentum 0.9, global_step + 1.  self.last_accuracy (device scalar)
+        is the batch accuracy of this step's training-mode forward pass, before the update."""
+        self.G.zero_()
+        self._forward(True)
+        for _ in self._backward_iter():
+            pass
+        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
+        ops.sum_f32(self.l2_partial, self.l2_sum)
+        self._fp_batch.run()
+        self.global_step += 1
+        # :128-130 compares pred (int64) with labels (int32), which TF 1.x refuses as written: the evident intent, mean(pred == label), is built
+        self.last_accuracy = self.correct.mean()
+        return self.ce.sum() / self.batch_size + self.weight_decay * self.l2_sum
+
+    def _train_pretraining_epoch(self, lr):
+        """RetinaNet.py:476-486: (mean loss, mean accuracy) over num_train // batch_size steps"""
+        if callable(self.train_initializer):
+            self.train_initializer()
+        mean_loss, mean_acc = [], []
+        num_iters = self.num_train // self.batch_size
+        it = iter(self.train_iterator)
+        for i in range(num_iters):
+            try:
+                images, labels = next(it)
+            except StopIteration:
+                it = iter(self.train_iterator)
+                images, labels = next(it)
+            self.set_batch(images, labels)
+            loss = float(self.train_step(lr).item())
+            acc = float(self.last_accuracy.item())
+            if self.verbose:
+                sys.stdout.write('\r>> ' + 'iters ' + str(i) + str('/') + str(num_iters) + ' loss ' + str(loss) + ' acc ' + str(acc))
+                sys.stdout.flush()
+            mean_loss.append(loss)
+            mean_acc.append(acc)
+        if self.verbose:
+            sys.stdout.write('\n')
+        return np.mean(mean_loss), np.mean(mean_acc)
+
+    def _test_one_pretraining_image(self, images):
+        """RetinaNet.py:501-503: the predicted class, int64 [1] (the fed tensor bypasses the mean subtraction unless test_subtract_mean)"""
+        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
+        if self.data_format == 'channels_first' and images.shape[1] == 3:
+            images = images.permute(0, 2, 3, 1)
+        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
+        self.images.copy_(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        return self.pred.cpu().numpy().astype(np.int64)
+
+    def export_pretraining_tf_variables(self):
+        """what the pre-training `tf.train.Saver(tf.trainable_variables('feature_extractor'))` (RetinaNet.py:548-551) writes: the kernels, biases,
+        gammas and betas of l0 .. l64 under the detection graph's names -- no moving statistics, no momentum slots, no global_step"""
+        return OrderedDict((tfname, self._logical(ours, self.P)) for tfname, ours in reference_variable_map(self.block_list).items() if ours in self.pinfo)
+
+    def _save_pretraining_weight(self, mode, path):
+        """RetinaNet.py:509-519.  'tf': exactly the trainables of the pre-training Saver; torch: the same trainables plus momentum and global_step
+        (to resume), marked as a pre-training file.  Both load into a detection model through load_pretraining_weight."""
+        assert (mode in ['latest', 'best'])
+        dirname = os.path.dirname(path)
+        if dirname and not os.path.exists(dirname):
+            os.makedirs(dirname)
+            print(dirname, 'does not exist, create it done')
+        prefix = path + '-' + str(self.global_step)
+        if self.config.get('checkpoint_format', 'torch') == 'tf':
+            from . import tf_checkpoint
+            tf_checkpoint.write_bundle(prefix, self.export_pretraining_tf_variables())
+            tf_checkpoint.update_checkpoint_state(prefix)
+        else:
+            blob = {'params': OrderedDict((k, self.get_param(k)) for k in self.pinfo), 'momentum': self.Mom.detach().cpu(), 'global_step': self.global_step,
+                    'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}, 'pretraining': True}
+            torch.save(blob, prefix)
+        print('save', mode, 'model in', path, 'successfully')
+
+    def _load_pretraining_model_weight(self, path):
+        """load_weight of the pre-training model: the trainables of l0 .. l64 (the pre-training Saver's variables) from a file of either format
+        and either graph; momentum and global_step too from a torch pre-training file of this layout"""
+        if os.path.exists(str(path) + '.index'):
+            stats = self.S.clone()
+            self.load_tf_checkpoint(path, backbone_only=True)
+            self.S.copy_(stats)                       # the pre-training Saver restores no moving statistics
+            print('load weight', path, 'successfully')
+            return
+        blob = torch.load(path, map_location='cpu', weights_only=True)
+        missing = [k for k in self.pinfo if k not in blob['params']]
+        if missing:
+            raise ValueError(f'{path}: {len(missing)} parameters of this model are not in the checkpoint (e.g. {missing[:3]})')
+        self.load_oracle_params({k: v for k, v in blob['params'].items() if k in self.pinfo})
+        if blob.get('pretraining') and dict(blob['layout']) == dict(self.pinfo):
+            self.Mom.copy_(blob['momentum'].to(self.dev))
+            self.global_step = int(blob.get('global_step', 0))
+        print('load weight', path, 'successfully')
 
 
 def reference_variable_map(block_list=(3, 4, 6, 3)):
