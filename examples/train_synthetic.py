@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """The reference's driver flow (testSSD300.py / testYOLOv3.py: config dict -> data provider -> model -> train_one_epoch ->
-save_weight -> test_one_image) on synthetic VOC-shaped pictures, with the GPU augmentor in front of the model.
+save_weight -> test_one_image) on synthetic VOC-shaped pictures, with the GPU augmentor in front of the model.  After every epoch the model is
+evaluated on a held-out synthetic validation set (VOC07 mAP, model.evaluate()) and saved as 'best' when the mAP improves.
 Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet] [epochs]
 
 What changes for a user of the reference:
@@ -49,7 +50,9 @@ class SyntheticVOC:
             yield self.aug(imgs, gts)
 
 
-data_provider = {'data_shape': [size, size, 3], 'num_train': 4 * batch_size, 'num_val': 0, 'train_generator': SyntheticVOC(4), 'val_generator': None}
+val_batches = list(SyntheticVOC(2, seed=1))      # held out: the same pictures at every evaluation
+data_provider = {'data_shape': [size, size, 3], 'num_train': 4 * batch_size, 'num_val': 2 * batch_size, 'train_generator': SyntheticVOC(4),
+                 'val_generator': val_batches}
 if which == 'ssd300':
     config = {'mode': 'train', 'data_format': 'channels_last', 'num_classes': 20, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'batch_size': batch_size,
               'nms_score_threshold': 0.5, 'nms_max_boxes': 20, 'nms_iou_threshold': 0.5, 'pretraining_weight': './vgg_16.ckpt'}   # testSSD300.py:15-32
@@ -66,11 +69,18 @@ else:
               'nms_score_threshold': 0.5, 'nms_max_boxes': 10, 'nms_iou_threshold': 0.5,
               'priors': [[[10., 13.], [16, 30.], [33., 23.]], [[30., 61.], [62., 45.], [59., 119.]], [[116., 90.], [156., 198.], [373., 326.]]]}  # testYOLOv3.py:17-41
     model = odtk.YOLOv3(config, data_provider)
+best_map = -1.0
 for epoch in range(epochs):
     print('-' * 20, 'epoch', epoch, '-' * 20)
     mean_loss = model.train_one_epoch(0.001)
     print('>> mean loss', mean_loss)
+    result = model.evaluate()                 # a test-mode copy of the model on the current weights; the training state is left as it is
+    mAP = 0.0 if np.isnan(result['mAP']) else result['mAP']
+    print('>> val mAP (VOC07) %.4f over %d images, %d detections' % (mAP, 2 * batch_size, int(result['num_detections'].sum())))
     model.save_weight('latest', os.path.join('/tmp', which, 'test'))
+    if mAP > best_map:
+        best_map = mAP
+        model.save_weight('best', os.path.join('/tmp', which, 'best'))
 test = type(model)(dict(config, mode='test'), None)
 test.load_weight(os.path.join('/tmp', which, 'test') + '-' + str(model.global_step))
 scores, bbox, class_id = test.test_one_image(np.random.default_rng(1).integers(0, 256, (1, size, size, 3)).astype(np.float32))

@@ -625,6 +625,23 @@ int odtk_lhrcnn_rcnn_decode(const float* logits, int ldl, const float* pbbox, in
                             float score_threshold, float* conf, float* boxes, unsigned char* cand, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Evaluation: PASCAL VOC average precision per class over a whole validation set (no reference counterpart: its val_generator is "not used",
+ * testSSD300.py:56-58).  Inputs, all device arrays: detections scores[D], boxes[D][4] (y1, x1, y2, x2 px), det_cls[D], det_img[D] (the order of
+ * the arrays is the sequence order that breaks score ties), ground truth gt_rows[G][5] (yc, xc, h, w, cls px; cls < 0 = padding, not counted) and
+ * gt_img[G].  Per class: detections ranked by score (descending, ties to the lower index); each one, in that order, takes the first GT row of its
+ * (image, class) with the largest IoU (f32, no +1 term) if that IoU > iou_thr and the row is not taken yet -> tp_out[i] = 1, else 0 (a duplicate is a
+ * false positive); npos_out[c] = GT rows of class c; ap_out[c] (f64) from the cumulative precision / recall: metric 0 = VOC07 11-point (t = k * 0.1),
+ * 1 = area under the interpolated curve (VOC2010+); NaN where npos_out[c] == 0.  IoU takes min / max as fminf / fmaxf and is 0 unless the union is > 0,
+ * so a box with non-finite coordinates is a miss.  Detections with a non-finite score or a class / image id out of range
+ * are ignored (tp 0).  Deterministic (integer atomics only).  Limits: D <= 8 Mi, G <= 2 Mi, 1 <= num_images <= 2^20, 1 <= num_classes <= 1024; beyond
+ * them both calls fail (workspace_bytes returns -1) with the message in odtk_last_error().  Pointers of an empty side (D or G == 0) may be NULL.
+ * ------------------------------------------------------------------------- */
+long long odtk_voc_eval_workspace_bytes(int num_det, int num_gt, int num_images, int num_classes);
+int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                  const int* gt_img, int num_gt, int num_images, int num_classes, float iou_thr, int metric, void* workspace,
+                  unsigned char* tp_out, int* npos_out, double* ap_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Collectives (SURVEY.md 8b's export list, 8e): the gradient sum of the data-parallel step for a binder that is not PyTorch.  No reference
  * counterpart (the reference is single-device, testSSD300.py:14).  A thin layer over RCCL (ring / tree all-reduce over xGMI), bound with dlopen at
  * first use: a missing RCCL fails these calls with a message and nothing else.  One communicator per process and GPU (the current HIP device at

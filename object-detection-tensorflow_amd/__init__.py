@@ -9,7 +9,8 @@ reached through the C-ABI in ``include/odtk.h`` (``libodtk.so``).
 from . import _lib                      # noqa: F401
 from ._lib import BF16, F32, F32X3, OdtkError  # noqa: F401
 
-__all__ = ["BF16", "F32", "OdtkError", "SSD300", "YOLOv3", "RetinaNet", "FCOS", "CenterNet", "SSD512", "RefineDet320", "PFPNetR", "YOLOv2", "LHRCNN"]
+__all__ = ["BF16", "F32", "OdtkError", "SSD300", "YOLOv3", "RetinaNet", "FCOS", "CenterNet", "SSD512", "RefineDet320", "PFPNetR", "YOLOv2", "LHRCNN",
+           "VOCEvaluator", "evaluate"]
 
 
 def __getattr__(name):
@@ -43,4 +44,7 @@ def __getattr__(name):
     if name == "LHRCNN":
         from .lhrcnn import LHRCNN
         return LHRCNN
+    if name in ("VOCEvaluator", "evaluate"):
+        from . import voc_eval
+        return getattr(voc_eval, name)
     raise AttributeError(name)

@@ -157,6 +157,8 @@ SIGNATURES = {
     "odtk_comm_allreduce": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
     "odtk_comm_broadcast": (_i, [_vp, _vp, _ll, _i, _i, _vp]),
     "odtk_comm_destroy": (_i, [_vp]),
+    "odtk_voc_eval_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "odtk_voc_eval": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -31,6 +31,7 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN = (0.485, 0.456, 0.406)                                  # CenterNet.py:52-53
@@ -83,7 +84,7 @@ class _Act:
         self.g = None                                          # gradient buffer (train mode, allocated by _build_backward)
 
 
-class CenterNet(F32Warmup):
+class CenterNet(EvaluateMixin, F32Warmup):
     OPT_BUFFERS = ('M1', 'M2')
     def __init__(self, config, data_provider):
         assert config['mode'] in ['train', 'test']

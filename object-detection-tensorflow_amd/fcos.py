@@ -27,6 +27,7 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -85,7 +86,7 @@ class _Act:
         self.gid = name
 
 
-class FCOS(F32Warmup):
+class FCOS(EvaluateMixin, F32Warmup):
     def __init__(self, config, data_provider):
         assert config['mode'] in ['train', 'test']
         assert config['data_format'] in ['channels_first', 'channels_last']

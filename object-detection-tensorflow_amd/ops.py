@@ -682,3 +682,22 @@ def lhrcnn_gather_rois(prop, sel, cnt, img_h, img_w, roi_box, roi_prop, roi_img)
 def lhrcnn_rcnn_decode(logits, ldl, pbbox, ldb, roi_prop, roi_img, Cn, thr, conf, boxes, cand):
     call("odtk_lhrcnn_rcnn_decode", _p(logits), ldl, _p(pbbox), ldb, _p(roi_prop), _p(roi_img), roi_img.shape[0], Cn, float(thr), _p(conf), _p(boxes), _p(cand),
          _stream())
+
+
+# ---------------------------------------------------------------- evaluation: PASCAL VOC AP (csrc/voc_eval.hip)
+VOC_METRICS = {'voc07': 0, 'area': 1}
+
+
+def voc_eval_workspace(D, G, I, C, device):
+    n = int(_lib.load().odtk_voc_eval_workspace_bytes(D, G, I, C))
+    if n < 0:
+        raise _lib.OdtkError(f"libodtk error: {_lib.load().odtk_last_error().decode()}")
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+
+
+def voc_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_classes, iou_thr, metric, ws, tp, npos, ap):
+    """scores f32[D], boxes f32[D,4], det_cls / det_img i32[D], gt_rows f32[G,5], gt_img i32[G] -> tp u8[D], npos i32[C], ap f64[C] (include/odtk.h)"""
+    D, G = scores.shape[0], gt_rows.shape[0]
+    e = lambda t: _p(t) if t.numel() else None      # noqa: E731 -- an empty side passes NULL
+    call("odtk_voc_eval", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), G, int(num_images), int(num_classes),
+         float(iou_thr), VOC_METRICS[metric], _p(ws), e(tp), _p(npos), _p(ap), _stream())

@@ -28,6 +28,7 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -76,7 +77,7 @@ class _Act:
         self.g = None
 
 
-class RefineDet320(F32Warmup):
+class RefineDet320(EvaluateMixin, F32Warmup):
     # RefineDet320 / PFPNetR do not pass the bf16 gate (one head layer loses its direction); YOLOv2 does.  Round 4: their default is the f32 engine with
     # ODTK_F32X3 convolution descriptors (three bf16 MFMA products per f32 product): it passes the same gate at RANDOM INITIALISATION (minimum cosine 0.998 / 0.999
     # against the exact f32 engine) at 2.1x the exact engine's throughput (607 / 598 against 282 / 286 images/s)

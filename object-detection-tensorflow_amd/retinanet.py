@@ -30,6 +30,7 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 
 MEAN_RGB = (123.68, 116.779, 103.979)
 FILTERS = (7, 14, 28, 56)                                     # RetinaNet.py:27 (sic)
@@ -88,7 +89,7 @@ class _Act:
         self.gid = name
 
 
-class RetinaNet:
+class RetinaNet(EvaluateMixin):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         assert config['mode'] in ['train', 'test']

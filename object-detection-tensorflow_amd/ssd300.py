@@ -31,6 +31,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 INPUT_SIZE = 300
@@ -142,7 +143,7 @@ class _Conv:
         self.bn, self.relu = bn, relu
 
 
-class SSD300(F32Warmup):
+class SSD300(EvaluateMixin, F32Warmup):
     # the variant: SSD512 (ssd512.py) overrides these
     INPUT_SIZE = INPUT_SIZE
     FEATURE_SIZES = FEATURE_SIZES

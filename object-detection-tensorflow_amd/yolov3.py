@@ -32,6 +32,7 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
+from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)                                       # YOLOv3.py:65
@@ -51,7 +52,7 @@ class _Act:
         self.gid = name
 
 
-class YOLOv3(F32Warmup):
+class YOLOv3(EvaluateMixin, F32Warmup):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         assert config['mode'] in ['train', 'test']

@@ -1,0 +1,153 @@
+"""Times the VOC evaluator (odtk.VOCEvaluator.result / csrc/voc_eval.hip) and end-to-end SSD300.evaluate; prints one JSON line.
+
+  * VOC07-test sized input: 4 952 images, 20 classes, ~100 detections and ~2.4 GT rows per image (seeded);
+  * stress: 100 000 images x 20 detections = 2 M detections of one class;
+  * per input: result() with device synchronisation (host packing, the one upload, the kernels, the read-back), the kernels alone (odtk_voc_eval
+    on uploaded tensors, HIP events) and the NumPy restatement (tests/voc_eval_ref.evaluate_fast) on 16 threads;
+  * SSD300.evaluate on the exact f32 engine (test mode, score threshold 0.01) in images/s, and the evaluator's share of it.
+Per-kernel times: run `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/eval_bench.py --kernels-only` separately."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import numpy as np      # noqa: E402
+import torch            # noqa: E402
+
+import odtk             # noqa: E402
+from odtk import ops    # noqa: E402
+import voc_eval_ref as R                # noqa: E402
+
+
+def synthetic(seed, n_img, C, det_per_img, gt_mean, one_class=None):
+    rng = np.random.default_rng(seed)
+    ng = np.clip(rng.poisson(gt_mean - 1, n_img) + 1, 1, 12) if gt_mean != int(gt_mean) else np.full(n_img, int(gt_mean))
+    dets, gts = [], []
+    for k in range(n_img):
+        n = int(ng[k])
+        yc, xc, h, w = rng.uniform(20, 280, n), rng.uniform(20, 280, n), rng.uniform(8, 120, n), rng.uniform(8, 120, n)
+        cls = rng.integers(0, C, n) if one_class is None else np.full(n, one_class)
+        g = np.stack([yc, xc, h, w, cls], 1).astype(np.float32)
+        j = rng.integers(0, n, det_per_img)
+        hit = rng.random(det_per_img) < 0.3
+        c = np.stack([yc - h / 2, xc - w / 2, yc + h / 2, xc + w / 2], 1)[j]
+        rnd = rng.uniform(0, 260, (det_per_img, 2))
+        box = np.where(hit[:, None], c + rng.normal(0, 4, (det_per_img, 4)), np.concatenate([rnd, rnd + rng.uniform(5, 80, (det_per_img, 2))], 1))
+        dc = np.where(hit, cls[j], rng.integers(0, C, det_per_img)) if one_class is None else np.full(det_per_img, one_class)
+        dets.append((rng.random(det_per_img).astype(np.float32), box.astype(np.float32), dc.astype(np.int32)))
+        gts.append(g)
+    return dets, gts
+
+
+def time_result(dets, gts, C, dev, reps):
+    ev = odtk.VOCEvaluator(C, device=dev)
+    for d, g in zip(dets, gts):
+        ev.add(list(d), g)
+    ev.result()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ev.result()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t)
+    return ev, 1e3 * float(np.median(ts))
+
+
+def time_kernels(ev, C, dev, reps):
+    scores, boxes, cls, img, gt, gi = ev._pack()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    args = [t(scores), t(boxes), t(cls), t(img), t(gt), t(gi)]
+    D, G, I = scores.shape[0], gt.shape[0], ev.num_images
+    ws = ops.voc_eval_workspace(D, G, I, C, dev)
+    tp = torch.empty(D, dtype=torch.uint8, device=dev)
+    npos = torch.empty(C, dtype=torch.int32, device=dev)
+    ap = torch.empty(C, dtype=torch.float64, device=dev)
+    run = lambda: ops.voc_eval(*args, I, C, 0.5, 'voc07', ws, tp, npos, ap)   # noqa: E731
+    run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def time_numpy(dets, gts, C):
+    t = time.perf_counter()
+    R.evaluate_fast(dets, gts, C)
+    return 1e3 * (time.perf_counter() - t)
+
+
+def ssd300_e2e(dev, n_images):
+    from oracle import ssd300_ref as SR
+    cfg = {'mode': 'test', 'data_format': 'channels_last', 'num_classes': 20, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'batch_size': 1,
+           'nms_score_threshold': 0.01, 'nms_max_boxes': 20, 'nms_iou_threshold': 0.5, 'pretraining_weight': '', 'verbose': False,
+           'compute_dtype': 'f32'}
+    p = SR.init_params(3)
+    imgs, _ = SR.synthetic_batch(2, 7)
+    SR.calibrate_bn(p, imgs, subtract_mean=False)
+    val = [tuple(t.numpy() for t in SR.synthetic_batch(4, 300 + i)) for i in range(n_images // 4)]
+    m = odtk.SSD300(cfg, None)
+    m.load_oracle_params(p)
+    m.evaluate(generator=val[:1])                                     # warm-up
+    spent = []
+    orig = odtk.VOCEvaluator.result
+
+    def timed(self):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        r = orig(self)
+        torch.cuda.synchronize()
+        spent.append(time.perf_counter() - t)
+        return r
+    odtk.VOCEvaluator.result = timed
+    try:
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        r = m.evaluate(generator=val)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t
+    finally:
+        odtk.VOCEvaluator.result = orig
+    return {'images': n_images, 'images_per_s': n_images / total, 'evaluate_ms': 1e3 * total, 'result_ms': 1e3 * spent[0],
+            'evaluator_share': spent[0] / total, 'detections': int(r['num_detections'].sum()), 'mAP': r['mAP']}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--e2e-images', type=int, default=256)
+    ap.add_argument('--kernels-only', action='store_true', help='a few kernel runs of both inputs (for rocprofv3 --kernel-trace --stats)')
+    a = ap.parse_args()
+    torch.set_num_threads(16)
+    os.environ.setdefault('OMP_NUM_THREADS', '16')
+    dev = torch.device('cuda:0')
+    out = {}
+    for name, spec in [('voc07', (0, 4952, 20, 100, 2.4, None)), ('stress_2m', (1, 100000, 20, 20, 2, 0))]:
+        t0 = time.perf_counter()
+        dets, gts = synthetic(*spec)
+        ev, ms_result = time_result(dets, gts, spec[2], dev, 1 if a.kernels_only else a.reps)
+        ms_kern = time_kernels(ev, spec[2], dev, 3 if a.kernels_only else a.reps)
+        row = {'images': spec[1], 'detections': sum(len(d[0]) for d in dets), 'gt_rows': sum(len(g) for g in gts),
+               'result_ms': ms_result, 'kernels_ms': ms_kern}
+        if not a.kernels_only:
+            row['numpy_ref_ms'] = time_numpy(dets, gts, spec[2])
+            row['speedup_kernels_vs_numpy'] = row['numpy_ref_ms'] / ms_kern
+            row['speedup_result_vs_numpy'] = row['numpy_ref_ms'] / ms_result
+        row['setup_s'] = time.perf_counter() - t0
+        out[name] = row
+        print(name, json.dumps(row), file=sys.stderr, flush=True)
+    if not a.kernels_only:
+        out['ssd300_evaluate_f32'] = ssd300_e2e(dev, a.e2e_images)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
