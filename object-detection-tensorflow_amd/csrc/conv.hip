@@ -1189,25 +1189,25 @@ extern "C" int odtk_conv2d_wgrad(const odtk_conv_desc* d, const void* x, const v
         a.dbg2 |= 4096;
     }
     if (!g_force_regstage && g_v3_mode != 1 && wgrad_f32_narrow_supported(a, d->dtype)) {
-        launch_wgrad_f32_narrow(a, (hipStream_t)stream);
+        if (int e = launch_wgrad_f32_narrow(a, (hipStream_t)stream)) return e;
         g_last_kernel = "wgrad_f32_narrow_kernel";
         ODTK_LAUNCH_CHECK();
         return ODTK_OK;
     }
     if (!g_force_regstage && g_v3_mode != 1 && !(g_dbg & 2048) && wgrad_c64_supported(a, d->dtype)) {
-        launch_wgrad_c64(a, (hipStream_t)stream);
+        if (int e = launch_wgrad_c64(a, (hipStream_t)stream)) return e;
         g_last_kernel = "wgrad3x3_c64k64_kernel";
         ODTK_LAUNCH_CHECK();
         return ODTK_OK;
     }
     if (!g_force_regstage && g_v3_mode != 1 && !(g_dbg & 2048) && wgrad_c8_supported(a, d->dtype)) {
-        launch_wgrad_c8(a, (hipStream_t)stream);
+        if (int e = launch_wgrad_c8(a, (hipStream_t)stream)) return e;
         g_last_kernel = "wgrad3x3_c8k64_kernel";
         ODTK_LAUNCH_CHECK();
         return ODTK_OK;
     }
     if (!g_force_regstage && g_v3_mode != 1 && wgrad_v3_supported(a, d->dtype)) {
-        launch_wgrad_v3(a, (hipStream_t)stream);
+        if (int e = launch_wgrad_v3(a, (hipStream_t)stream)) return e;
         g_last_kernel = a.which == 8 ? "conv_wgrad_v8_kernel" : "conv_wgrad_v3_kernel";
         ODTK_LAUNCH_CHECK();
         return ODTK_OK;

@@ -2888,6 +2888,8 @@ __global__ void __launch_bounds__(256) conv_wgrad_v8_kernel(const WgradArgs a) {
 int wgrad_split_scratch(WgradArgs& a, int splits, int bias_slots, hipStream_t st) {
     a.ws = nullptr; a.bws = nullptr; a.nsplit = splits; a.nbslot = bias_slots;
     if (splits < 2 || !g_wgrad_deterministic) return 0;
+    // wgrad_split_reduce adds the partials as rows of four floats (check_desc keeps C a multiple of the 16-byte chunk, so this holds for every descriptor it lets through)
+    ODTK_REQUIRE(((long long)a.K * a.RSC) % 4 == 0, "conv2d_wgrad: the fixed-order reduction needs K * R * S * C = %lld to be a multiple of 4", (long long)a.K * a.RSC);
     float* base = nullptr;
     const size_t wbytes = (size_t)splits * a.K * a.RSC * sizeof(float);
     if (int e = conv_scratch(wbytes + (size_t)bias_slots * a.K * sizeof(float), st, &base)) return e;
