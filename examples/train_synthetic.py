@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's driver flow (testSSD300.py / testYOLOv3.py: config dict -> data provider -> model -> train_one_epoch ->
 save_weight -> test_one_image) on synthetic VOC-shaped pictures, with the GPU augmentor in front of the model.  After every epoch the model is
-evaluated on a held-out synthetic validation set (VOC07 mAP, model.evaluate()) and saved as 'best' when the mAP improves.
+evaluated on a held-out synthetic validation set (VOC07 mAP, model.evaluate(batch_size=...): batched inference) and saved as 'best' when the mAP improves.
 Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet] [epochs]
 
 What changes for a user of the reference:
@@ -74,7 +74,8 @@ for epoch in range(epochs):
     print('-' * 20, 'epoch', epoch, '-' * 20)
     mean_loss = model.train_one_epoch(0.001)
     print('>> mean loss', mean_loss)
-    result = model.evaluate()                 # a test-mode copy of the model on the current weights; the training state is left as it is
+    # a test-mode copy of the model on the current weights, `batch_size` validation images per forward pass (test_images); the training state is left as it is
+    result = model.evaluate(batch_size=batch_size)
     mAP = 0.0 if np.isnan(result['mAP']) else result['mAP']
     print('>> val mAP (VOC07) %.4f over %d images, %d detections' % (mAP, 2 * batch_size, int(result['num_detections'].sum())))
     model.save_weight('latest', os.path.join('/tmp', which, 'test'))

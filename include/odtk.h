@@ -398,6 +398,43 @@ int odtk_nms_batched(const float* boxes, long long box_stride, const float* scor
                      const int* max_out_dev, int max_out_stride, int max_out_const,
                      float iou_threshold, int* out_idx, int cap, int* out_cnt, void* stream);
 
+/* ---- batched inference tail (csrc/detect_batched.hip): decode -> [row compaction] -> image x class NMS -> detection pack, N images per launch ----
+ *
+ * Decode of N images: the arithmetic and outputs of odtk_ssd_decode / odtk_retina_decode per image (the same kernel, one y-block per image), priors /
+ * anchors shared.  pred [N][A][ld] (SSD family) or pconf [N][A][C] + pbox [N][A][4] (RetinaNet); conf, cand [N][A][C-1], boxes [N][A][4], keep [N][A]. */
+int odtk_ssd_decode_batched(const float* pred, int N, int A, int C, int ld, const float* yx, const float* hw, float score_thr, float* conf,
+                            float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
+int odtk_retina_decode_batched(const float* pconf, const float* pbox, int N, int A, int C, const float* yx, const float* hw, float score_thr,
+                               float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
+
+/* Greedy NMS for N * num_classes problems in one launch chain.  Problem (img, c): boxes at boxes + img*box_istride (floats) [n][4]; score i at
+ * scores[img*score_istride + c*score_cstride + i*score_estride]; valid[img*valid_istride + c*valid_cstride + i*valid_estride] (u8, NULL = all valid) must
+ * equal `valid_value`; n_dev (device ints [N], or NULL) limits image img to its first min(n, n_dev[img]) boxes.  Picks in order go to
+ * out_idx[(img*num_classes + c)*cap + j], the count to out_cnt[img*num_classes + c].  The kernels are those of odtk_nms_batched: every problem's picks, their
+ * order (lower index first on equal scores) and the count are what odtk_nms_batched gives on that image alone.  n <= 32768, N * num_classes <= 65535. */
+int odtk_nms_image_class(const float* boxes, long long box_istride, const float* scores, long long score_istride, long long score_cstride,
+                         int score_estride, const unsigned char* valid, long long valid_istride, long long valid_cstride, int valid_estride,
+                         int valid_value, int n, const int* n_dev, int N, int num_classes, int max_out, float iou_threshold, int* out_idx, int cap,
+                         int* out_cnt, void* stream);
+
+/* Order-preserving row compaction: per image, the ascending indices of the rows of cand [N][A][ld] (u8) with a non-zero byte among the first num_classes,
+ * rows [N][cap_rows] (the first cap_rows of them), counts [N] = how many there are (may exceed cap_rows: the caller checks).  Ballot + scan, no atomics. */
+int odtk_compact_rows(const unsigned char* cand, int N, int A, int ld, int num_classes, int cap_rows, int* rows, int* counts, void* stream);
+
+/* The compacted rows' operands for the NMS: conf_out / cand_out [N][cap_rows][num_classes], boxes_out [N][cap_rows][4] from conf [N][A][ldc], cand
+ * [N][A][ldk], boxes [N][A][4]; row j < min(counts[img], cap_rows) of image img is row rows[img][j].  Rows behind the count are not written. */
+int odtk_gather_rows(const int* rows, const int* counts, int N, int A, int cap_rows, int num_classes, const float* conf, int ldc,
+                     const float* boxes, const unsigned char* cand, int ldk, float* conf_out, float* boxes_out, unsigned char* cand_out,
+                     void* stream);
+
+/* Detection pack: from the NMS tables nms_idx [N][num_classes][cap] / nms_cnt [N][num_classes] and the operands the NMS ran on (score of row i, class c of
+ * image img at conf[img*conf_istride + i*ldc + c], its box at boxes[img*box_istride + 4 i]): counts [N] (detections per image), offsets [N + 1] (their
+ * exclusive scan, offsets[N] = K) and scores f32[K], bbox f32[K][4], class_id i32[K] ordered by image, then ascending class, then NMS pick order.  The
+ * three arrays need room for N * num_classes * cap rows.  N <= 1024. */
+int odtk_detection_pack(const int* nms_idx, const int* nms_cnt, int N, int num_classes, int cap, const float* conf, long long conf_istride, int ldc,
+                        const float* boxes, long long box_istride, int* counts, int* offsets, float* scores, float* bbox, int* class_id,
+                        void* stream);
+
 /* SSD300._compute_one_image_loss steps 8-12 (SSD300.py:427-453) + the batch mean
  * (SSD300.py:148) and its gradient.  loss_parts[N][4] = {neg, pos_conf, coord, total};
  * dpred [N][A][ld] is overwritten with d(sum_i total_i * grad_scale)/dpred. */

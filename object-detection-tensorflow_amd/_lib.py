@@ -140,6 +140,12 @@ SIGNATURES = {
     "odtk_augment_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "odtk_augment_boxes": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "odtk_augment_images": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "odtk_ssd_decode_batched": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_retina_decode_batched": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_nms_image_class": (_i, [_vp, _ll, _vp, _ll, _ll, _i, _vp, _ll, _ll, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp]),
+    "odtk_compact_rows": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "odtk_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "odtk_detection_pack": (_i, [_vp, _vp, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_ssd_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "odtk_depthwise_conv": (_i, [_vp, _i, _vp, _vp, _i] + [_i] * 9 + [_vp]),
     "odtk_depthwise_wgrad": (_i, [_vp, _i, _vp, _i, _vp] + [_i] * 7 + [_vp]),

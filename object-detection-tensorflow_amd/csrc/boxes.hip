@@ -214,6 +214,9 @@ __device__ __forceinline__ unsigned sortable(float f) {
 }
 
 struct NBox { float ymin, xmin, ymax, xmax; };
+__device__ __forceinline__ long long nms_base(int b, int group, long long gstride, long long stride) {
+    return (long long)(b / group) * gstride + (long long)(b % group) * stride;
+}
 
 __device__ __forceinline__ NBox norm_box(float b0, float b1, float b2, float b3) {
     NBox r;
@@ -232,11 +235,15 @@ __device__ __forceinline__ float iou_nms(const NBox& a, const NBox& b) {
     return inter / (area_a + area_b - inter);
 }
 
+// Problem b = (g, c) with g = b / group, c = b % group: its operands start at g * <x>_gstride + c * <x>_stride.  odtk_nms_batched sets group = 1 (g = b, c = 0:
+// the one stride per operand of its interface); the image x class form (odtk_nms_image_class) has g = image, c = class.
 struct NmsArgs {
-    const float* boxes; long long box_stride;
-    const float* scores; long long score_bstride; int score_estride;
-    const unsigned char* valid; long long valid_bstride; int valid_estride; int valid_value;
+    int group;
+    const float* boxes; long long box_gstride, box_stride;
+    const float* scores; long long score_gstride, score_bstride; int score_estride;
+    const unsigned char* valid; long long valid_gstride, valid_bstride; int valid_estride; int valid_value;
     int n, SZ;
+    const int* n_dev;               // or null: per-group box count (device ints), problem b looks at its first min(n, n_dev[b / group]) boxes
     const int* max_out_dev; int max_out_stride; int max_out_const;
     float thr;
     int* out_idx; int cap; int* out_cnt;
@@ -266,6 +273,8 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_kernel(const NmsArgs a, const
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
     __shared__ int s_nvalid;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long sbase = nms_base(b, a.group, a.score_gstride, a.score_bstride), vbase = nms_base(b, a.group, a.valid_gstride, a.valid_bstride);
+    const int n_eff = a.n_dev ? min(a.n, max(a.n_dev[b / a.group], 0)) : a.n;
     if (MODE == 0 && use_flags && ws.info[b * 4 + 3] == 0) return;
     const int SZ = a.SZ;
     if (tid == 0) s_nvalid = 0;
@@ -273,10 +282,10 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_kernel(const NmsArgs a, const
     int myvalid = 0;
     for (int i = tid; i < SZ; i += NMS_THREADS) {
         unsigned long long key = 0ull;
-        if (i < a.n) {
+        if (i < n_eff) {
             bool ok = true;
-            if (a.valid) ok = a.valid[b * a.valid_bstride + (long long)i * a.valid_estride] == (unsigned char)a.valid_value;
-            const float s = a.scores[b * a.score_bstride + (long long)i * a.score_estride];
+            if (a.valid) ok = a.valid[vbase + (long long)i * a.valid_estride] == (unsigned char)a.valid_value;
+            const float s = a.scores[sbase + (long long)i * a.score_estride];
             if (ok && s > -INFINITY) {           // score > lowest(); NaN excluded
                 key = ((unsigned long long)sortable(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
                 ++myvalid;
@@ -318,7 +327,7 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_kernel(const NmsArgs a, const
     int mo = a.max_out_dev ? a.max_out_dev[(long long)b * a.max_out_stride] : a.max_out_const;
     if (mo > a.cap) mo = a.cap;
     if (mo < 0) mo = 0;
-    const float* boxes = a.boxes + b * a.box_stride;
+    const float* boxes = a.boxes + nms_base(b, a.group, a.box_gstride, a.box_stride);
     if (MODE == 1) {
         // candidates the scan may have to visit: mo picks + a margin for suppressed ones
         int lim = (mo + mo / 2 + 256 + 63) & ~63;
@@ -417,14 +426,16 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_topk_kernel(const NmsArgs a, 
     // 120-KiB workgroup in the middle of the small-kernel chain starts ~80 us late)
     __shared__ int s_nvalid, s_B, s_cnt, s_pos, s_hi;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long sbase = nms_base(b, a.group, a.score_gstride, a.score_bstride), vbase = nms_base(b, a.group, a.valid_gstride, a.valid_bstride);
+    const int n_eff = a.n_dev ? min(a.n, max(a.n_dev[b / a.group], 0)) : a.n;
     int mo = a.max_out_dev ? a.max_out_dev[(long long)b * a.max_out_stride] : a.max_out_const;
     if (mo > a.cap) mo = a.cap;
     if (mo < 0) mo = 0;
-    const float* boxes = a.boxes + b * a.box_stride;
+    const float* boxes = a.boxes + nms_base(b, a.group, a.box_gstride, a.box_stride);
     auto make_key = [&](int i) -> unsigned long long {
         bool ok = true;
-        if (a.valid) ok = a.valid[b * a.valid_bstride + (long long)i * a.valid_estride] == (unsigned char)a.valid_value;
-        const float s = a.scores[b * a.score_bstride + (long long)i * a.score_estride];
+        if (a.valid) ok = a.valid[vbase + (long long)i * a.valid_estride] == (unsigned char)a.valid_value;
+        const float s = a.scores[sbase + (long long)i * a.score_estride];
         if (!(ok && s > -INFINITY)) return 0ull;
         return ((unsigned long long)sortable(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
     };
@@ -433,9 +444,9 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_topk_kernel(const NmsArgs a, 
     if (tid == 0) { s_nvalid = 0; s_B = -1; s_cnt = 0; s_pos = 0; s_hi = 0; }
     __syncthreads();
     int myvalid = 0;
-    for (int i0 = 0; i0 < a.n; i0 += NMS_THREADS) {             // (whole waves enter hist_add: its ballots need every lane)
+    for (int i0 = 0; i0 < n_eff; i0 += NMS_THREADS) {             // (whole waves enter hist_add: its ballots need every lane)
         const int i = i0 + tid;
-        const unsigned long long key = i < a.n ? make_key(i) : 0ull;
+        const unsigned long long key = i < n_eff ? make_key(i) : 0ull;
         hist_add(hist, (unsigned)(key >> 52), key != 0ull, lane);
         if (key) ++myvalid;
     }
@@ -466,9 +477,9 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_topk_kernel(const NmsArgs a, 
             if (tid == 0) { s_B = -1; s_cnt = 0; s_hi = 0; }
             __syncthreads();
             const unsigned dmask = (1u << width) - 1u;
-            for (int i0 = 0; i0 < a.n; i0 += NMS_THREADS) {
+            for (int i0 = 0; i0 < n_eff; i0 += NMS_THREADS) {
                 const int i = i0 + tid;
-                const unsigned long long key = i < a.n ? make_key(i) : 0ull;
+                const unsigned long long key = i < n_eff ? make_key(i) : 0ull;
                 hist_add(hist, (unsigned)(key >> shift) & dmask, key != 0ull && (key >> (shift + width)) == prefix, lane);
             }
             __syncthreads();
@@ -514,7 +525,7 @@ __global__ void __launch_bounds__(NMS_THREADS) nms_topk_kernel(const NmsArgs a, 
         if (tid == 0) { ws.info[b * 4 + 0] = 0; ws.info[b * 4 + 1] = nvalid; ws.info[b * 4 + 2] = mo; ws.info[b * 4 + 3] = 2; }
         return;
     }
-    for (int i = tid; i < a.n; i += NMS_THREADS) {
+    for (int i = tid; i < n_eff; i += NMS_THREADS) {
         const unsigned long long key = make_key(i);
         if (key && key >= thr_key) sel[atomicAdd(&s_pos, 1)] = key;
     }
@@ -836,13 +847,22 @@ __global__ void __launch_bounds__(64) ssd_loss_final_kernel(const LossArgs a) {
 // ------------------------------------------------------------------ inference decode
 // `box` / `ldb`: the 4 box regressions of anchor a are box[a * ldb .. +3] (SSD300: pred + C with the row pitch of
 // pred; RetinaNet: its own [A][4] tensor)
-__global__ void ssd_decode_kernel(const float* __restrict__ pred, int A, int C, int ld, const float* __restrict__ box, int ldb,
-                                  const float* __restrict__ yx,
-                                  const float* __restrict__ hw, float thr, float* __restrict__ conf,
-                                  float* __restrict__ boxes, unsigned char* __restrict__ keep,
-                                  unsigned char* __restrict__ cand) {
+// blockIdx.y = image: its rows start at pred + img * pred_istride / box + img * box_istride, its outputs at image img of [N][A][C-1] / [N][A][4] / [N][A]
+// (the single-image entry points launch one y-block with zero strides: the same kernel, so the batched tail agrees with them bit for bit)
+__global__ void ssd_decode_kernel(const float* __restrict__ pred_all, long long pred_istride, int A, int C, int ld, const float* __restrict__ box_all,
+                                  long long box_istride, int ldb, const float* __restrict__ yx,
+                                  const float* __restrict__ hw, float thr, float* __restrict__ conf_all,
+                                  float* __restrict__ boxes_all, unsigned char* __restrict__ keep_all,
+                                  unsigned char* __restrict__ cand_all) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= A) return;
+    const size_t img = blockIdx.y;
+    const float* pred = pred_all + img * pred_istride;
+    const float* box = box_all + img * box_istride;
+    float* conf = conf_all + img * (size_t)A * (C - 1);
+    float* boxes = boxes_all + img * (size_t)A * 4;
+    unsigned char* keep = keep_all + img * (size_t)A;
+    unsigned char* cand = cand_all + img * (size_t)A * (C - 1);
     const float* z = pred + (size_t)a * ld;
     const float* zb = box + (size_t)a * ldb;
     float m = z[0];
@@ -979,26 +999,13 @@ namespace odtk {
 void set_nms_legacy(bool on) { g_nms_legacy = on; }
 }  // namespace odtk
 
-extern "C" int odtk_nms_batched(const float* boxes, long long box_stride, const float* scores,
-                                long long score_bstride, int score_estride, const unsigned char* valid,
-                                long long valid_bstride, int valid_estride, int valid_value, int n, int B,
-                                const int* max_out_dev, int max_out_stride, int max_out_const,
-                                float iou_threshold, int* out_idx, int cap, int* out_cnt, void* stream) {
-    ODTK_REQUIRE(boxes && scores && out_idx && out_cnt, "nms: null pointer");
-    ODTK_REQUIRE(n > 0 && n <= 32768, "nms: n=%d out of range (1..32768)", n);
-    ODTK_REQUIRE(B > 0 && cap > 0, "nms: B and cap must be positive");
-    ODTK_REQUIRE(((uintptr_t)boxes % 16) == 0 && (box_stride % 4) == 0, "nms: boxes must be 16-byte aligned");
-    NmsArgs a;
-    a.boxes = boxes; a.box_stride = box_stride;
-    a.scores = scores; a.score_bstride = score_bstride; a.score_estride = score_estride;
-    a.valid = valid; a.valid_bstride = valid_bstride; a.valid_estride = valid_estride; a.valid_value = valid_value;
-    a.n = n;
+namespace odtk {
+namespace {
+int nms_launch(NmsArgs a, int B, float iou_threshold, hipStream_t st) {
     int SZ = 64;
-    while (SZ < n) SZ <<= 1;
+    while (SZ < a.n) SZ <<= 1;
     a.SZ = SZ;
-    a.max_out_dev = max_out_dev; a.max_out_stride = max_out_stride; a.max_out_const = max_out_const;
     a.thr = iou_threshold;
-    a.out_idx = out_idx; a.cap = cap; a.out_cnt = out_cnt;
     const bool big = SZ > 16384;
     const size_t lds = big ? 0 : (size_t)SZ * 8;
     static bool attr_set = false;
@@ -1007,7 +1014,6 @@ extern "C" int odtk_nms_batched(const float* boxes, long long box_stride, const 
         ODTK_CHECK_HIP(hipFuncSetAttribute((const void*)nms_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
         attr_set = true;
     }
-    hipStream_t st = (hipStream_t)stream;
     NmsScratch ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (int e = nms_scratch(B, &ws, big)) return e;
     if (g_nms_legacy) {
@@ -1019,11 +1025,59 @@ extern "C" int odtk_nms_batched(const float* boxes, long long box_stride, const 
     // split path: sort -> suppression bit matrix -> scan (+ whole-problem fallback for flagged problems)
     hipLaunchKernelGGL(nms_topk_kernel, dim3(B), dim3(NMS_THREADS), 4096 * 4 + NMS_TCAP * 8 + 64, st, a, ws);
     hipLaunchKernelGGL(nms_matrix_kernel, dim3(B >= 64 ? 32 : (B >= 16 ? 64 : 128), B), dim3(256), 0, st, ws, iou_threshold);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(64), 0, st, ws, out_idx, cap, out_cnt);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(64), 0, st, ws, a.out_idx, a.cap, a.out_cnt);
     if (big) hipLaunchKernelGGL((nms_kernel<0, true>), dim3(B), dim3(NMS_THREADS), 0, st, a, ws, 1);
     else hipLaunchKernelGGL(nms_kernel<0>, dim3(B), dim3(NMS_THREADS), lds, st, a, ws, 1);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
+}
+}  // namespace
+
+// csrc/detect_batched.hip (odtk_nms_image_class): problem (img, c) of N * nc -- image img's boxes, class c's score and candidate column.  The kernels are those
+// of odtk_nms_batched with the two-level operand addressing of NmsArgs, so every problem's picks, order and count are the ones odtk_nms_batched gives on that
+// image alone.
+int nms_image_class_launch(const float* boxes, long long box_istride, const float* scores, long long score_istride, long long score_cstride, int score_estride,
+                           const unsigned char* valid, long long valid_istride, long long valid_cstride, int valid_estride, int valid_value, int n, const int* n_dev,
+                           int N, int nc, int max_out, float iou_threshold, int* out_idx, int cap, int* out_cnt, void* stream) {
+    NmsArgs a;
+    a.group = nc;
+    a.boxes = boxes; a.box_gstride = box_istride; a.box_stride = 0;
+    a.scores = scores; a.score_gstride = score_istride; a.score_bstride = score_cstride; a.score_estride = score_estride;
+    a.valid = valid; a.valid_gstride = valid_istride; a.valid_bstride = valid_cstride; a.valid_estride = valid_estride; a.valid_value = valid_value;
+    a.n = n; a.n_dev = n_dev;
+    a.max_out_dev = nullptr; a.max_out_stride = 0; a.max_out_const = max_out;
+    a.out_idx = out_idx; a.cap = cap; a.out_cnt = out_cnt;
+    return nms_launch(a, N * nc, iou_threshold, (hipStream_t)stream);
+}
+
+// the decode launch of odtk_ssd_decode / odtk_retina_decode for N images (csrc/detect_batched.hip)
+int decode_launch(const float* pred, long long pred_istride, int N, int A, int C, int ld, const float* box, long long box_istride, int ldb, const float* yx,
+                  const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream) {
+    hipLaunchKernelGGL(ssd_decode_kernel, dim3(ceil_div(A, 256), N), dim3(256), 0, (hipStream_t)stream, pred, pred_istride, A, C, ld, box, box_istride, ldb, yx,
+                       hw, score_thr, conf, boxes, keep, cand);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+}  // namespace odtk
+
+extern "C" int odtk_nms_batched(const float* boxes, long long box_stride, const float* scores,
+                                long long score_bstride, int score_estride, const unsigned char* valid,
+                                long long valid_bstride, int valid_estride, int valid_value, int n, int B,
+                                const int* max_out_dev, int max_out_stride, int max_out_const,
+                                float iou_threshold, int* out_idx, int cap, int* out_cnt, void* stream) {
+    ODTK_REQUIRE(boxes && scores && out_idx && out_cnt, "nms: null pointer");
+    ODTK_REQUIRE(n > 0 && n <= 32768, "nms: n=%d out of range (1..32768)", n);
+    ODTK_REQUIRE(B > 0 && cap > 0, "nms: B and cap must be positive");
+    ODTK_REQUIRE(((uintptr_t)boxes % 16) == 0 && (box_stride % 4) == 0, "nms: boxes must be 16-byte aligned");
+    NmsArgs a;
+    a.group = 1;
+    a.boxes = boxes; a.box_gstride = box_stride; a.box_stride = 0;
+    a.scores = scores; a.score_gstride = score_bstride; a.score_bstride = 0; a.score_estride = score_estride;
+    a.valid = valid; a.valid_gstride = valid_bstride; a.valid_bstride = 0; a.valid_estride = valid_estride; a.valid_value = valid_value;
+    a.n = n; a.n_dev = nullptr;
+    a.max_out_dev = max_out_dev; a.max_out_stride = max_out_stride; a.max_out_const = max_out_const;
+    a.out_idx = out_idx; a.cap = cap; a.out_cnt = out_cnt;
+    return nms_launch(a, B, iou_threshold, (hipStream_t)stream);
 }
 
 extern "C" int odtk_ssd_loss(const float* pred, int N, int A, int C, int ld, const float* yx, const float* hw,
@@ -1053,10 +1107,7 @@ extern "C" int odtk_ssd_decode(const float* pred0, int A, int C, int ld, const f
                                unsigned char* cand, void* stream) {
     ODTK_REQUIRE(pred0 && yx && hw && conf && boxes && keep && cand, "ssd_decode: null pointer");
     ODTK_REQUIRE(C > 1 && C <= MAXC && ld >= C + 4, "ssd_decode: C=%d ld=%d unsupported", C, ld);
-    hipLaunchKernelGGL(ssd_decode_kernel, dim3(ceil_div(A, 256)), dim3(256), 0, (hipStream_t)stream, pred0, A, C, ld, pred0 + C, ld, yx,
-                       hw, score_thr, conf, boxes, keep, cand);
-    ODTK_LAUNCH_CHECK();
-    return ODTK_OK;
+    return decode_launch(pred0, 0, 1, A, C, ld, pred0 + C, 0, ld, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }
 
 // RetinaNet inference branch up to the per-class NMS loop (RetinaNet.py:224-238): same arithmetic, separate tensors
@@ -1065,8 +1116,5 @@ extern "C" int odtk_retina_decode(const float* pconf, const float* pbox, int A, 
                                   void* stream) {
     ODTK_REQUIRE(pconf && pbox && yx && hw && conf && boxes && keep && cand, "retina_decode: null pointer");
     ODTK_REQUIRE(C > 1 && C <= MAXC && A > 0, "retina_decode: C=%d A=%d unsupported", C, A);
-    hipLaunchKernelGGL(ssd_decode_kernel, dim3(ceil_div(A, 256)), dim3(256), 0, (hipStream_t)stream, pconf, A, C, C, pbox, 4, yx,
-                       hw, score_thr, conf, boxes, keep, cand);
-    ODTK_LAUNCH_CHECK();
-    return ODTK_OK;
+    return decode_launch(pconf, 0, 1, A, C, C, pbox, 0, 4, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }

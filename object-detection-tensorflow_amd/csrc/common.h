@@ -68,4 +68,11 @@ inline size_t dtype_size(int dt) { return dt == ODTK_F32 ? 4 : 2; }
 // d(pred) came back as 0x48600000 / 0x70200000 patterns, depending on the host heap layout), api.hip.
 int zero_async(void* p, size_t bytes, hipStream_t st);
 
+// boxes.hip: the NMS and decode launches behind the batched inference tail (csrc/detect_batched.hip)
+int nms_image_class_launch(const float* boxes, long long box_istride, const float* scores, long long score_istride, long long score_cstride, int score_estride,
+                           const unsigned char* valid, long long valid_istride, long long valid_cstride, int valid_estride, int valid_value, int n, const int* n_dev,
+                           int N, int nc, int max_out, float iou_threshold, int* out_idx, int cap, int* out_cnt, void* stream);
+int decode_launch(const float* pred, long long pred_istride, int N, int A, int C, int ld, const float* box, long long box_istride, int ldb, const float* yx,
+                  const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
+
 }  // namespace odtk

@@ -2,7 +2,8 @@
 per-class NMS (the SSD300 NMS path) -> [scores f32[K], bbox f32[K,4] y1x1y2x2 px, class_id i32[K]], i.e. what each class
 stores in `self.detection_pred` (RetinaNet.py:224-256, YOLOv3.py:320-368, FCOS.py:197-265, CenterNet.py:159-185, RefineDet.py:189-230);
 for RefineDet also the training-side chain matching -> ARM hard-negative mining -> two-stage loss (`refinedet_loss`).
-Inputs are the head outputs of ONE image as device tensors.  Product path: no CPU fallback, no use of the test oracles."""
+Inputs are the head outputs of ONE image as device tensors; `BatchedTail` is the same tail for N images per launch (test_images).  Product path: no CPU
+fallback, no use of the test oracles."""
 from __future__ import annotations
 
 import torch
@@ -37,6 +38,83 @@ def _per_class_nms(conf, boxes, cand, num_classes, max_boxes, iou_thr):
         scores.append(conf[ids, c]); bbox.append(boxes[ids])
         cid.append(torch.full((cnt[c],), c, dtype=torch.int32, device=dev))
     return torch.cat(scores), torch.cat(bbox, 0).reshape(-1, 4), torch.cat(cid)
+
+
+class BatchedTail:
+    """The inference tail behind the decode for N images at once: [order-preserving row compaction when a head has more rows than the NMS takes per problem]
+    -> NMS of N * num_classes problems in one launch chain (odtk_nms_image_class) -> detection pack (odtk_detection_pack) -> ONE read-back per batch (the
+    per-image counts, their scan and the packed rows, through a pinned host buffer).  Per image the result is what `_per_class_nms` returns for that image
+    alone, bit for bit: the same NMS kernels on the same operands, the same order (ascending class id, NMS pick order inside).  Buffers are allocated once
+    per (N, A, num_classes, max_boxes).  conf [N, A, ld] scores (classes in the first num_classes columns), boxes [N, A, 4], cand [N, A, ld] uint8."""
+
+    def __init__(self, N, A, num_classes, max_boxes, device):
+        self.N, self.A, self.nc, self.max_boxes = int(N), int(A), int(num_classes), int(max_boxes)
+        dev = self.dev = torch.device(device)
+        N, nc = self.N, self.nc
+        cap = self.cap = max(self.max_boxes, 1)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.compact = self.A > NMS_MAX_CANDIDATES
+        if self.compact:
+            R = self.R = NMS_MAX_CANDIDATES
+            self.rows = torch.zeros(N, R, **i32)
+            self.c_conf = torch.zeros(N, R, nc, device=dev)
+            self.c_boxes = torch.zeros(N, R, 4, device=dev)
+            self.c_cand = torch.zeros(N, R, nc, dtype=torch.uint8, device=dev)
+        self.out_idx = torch.zeros(N, nc, cap, **i32)
+        self.out_cnt = torch.zeros(N, nc, **i32)
+        # what travels back, one buffer of 4-byte words: counts [N] | offsets [N + 1] | compaction counts [N] | scores [K] | bbox [K, 4] | class_id [K]
+        K = self.K = N * nc * cap
+        self.words = torch.zeros(3 * N + 1 + 6 * K, **i32)
+        o = 0
+        self.counts = self.words[o: o + N]; o += N
+        self.offsets = self.words[o: o + N + 1]; o += N + 1
+        self.row_cnt = self.words[o: o + N]; o += N
+        self._o_scores, self._o_bbox, self._o_cid = o, o + K, o + 5 * K
+        self.scores = self.words[o: o + K].view(torch.float32); o += K
+        self.bbox = self.words[o: o + 4 * K].view(torch.float32).view(K, 4); o += 4 * K
+        self.class_id = self.words[o: o + K]
+        self.host = torch.zeros(self.words.shape, dtype=torch.int32, pin_memory=True) if dev.type == 'cuda' else None
+
+    def launch(self, conf, boxes, cand, iou_thr):
+        """the device side (no synchronisation): after it self.words holds the batch's detections"""
+        N, A, nc = self.N, self.A, self.nc
+        assert tuple(conf.shape[:2]) == (N, A) and tuple(boxes.shape) == (N, A, 4) and tuple(cand.shape) == tuple(conf.shape)
+        ld = conf.shape[2]
+        if self.compact:
+            R = self.R
+            ops.compact_rows(cand, nc, R, self.rows, self.row_cnt)
+            ops.gather_rows(self.rows, self.row_cnt, nc, conf, boxes, cand, self.c_conf, self.c_boxes, self.c_cand)
+            conf, boxes = self.c_conf, self.c_boxes
+            ops.nms_image_class(boxes, R * 4, conf, R * nc, 1, nc, self.c_cand, R * nc, 1, nc, 1, R, self.row_cnt, N, nc, self.max_boxes, iou_thr,
+                                self.out_idx, self.cap, self.out_cnt)
+        else:
+            ops.nms_image_class(boxes, A * 4, conf, A * ld, 1, ld, cand, A * ld, 1, ld, 1, A, None, N, nc, self.max_boxes, iou_thr,
+                                self.out_idx, self.cap, self.out_cnt)
+        ops.detection_pack(self.out_idx, self.out_cnt, conf, boxes, self.counts, self.offsets, self.scores, self.bbox, self.class_id)
+
+    def read(self, n_images=None):
+        """the one read-back: list of [scores f32[K], bbox f32[K, 4], class_id i32[K]] (numpy) of the first n_images images"""
+        n_images = self.N if n_images is None else int(n_images)
+        if self.host is not None:
+            self.host.copy_(self.words, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            h = self.host.numpy()
+        else:
+            h = self.words.numpy()
+        N, K = self.N, self.K
+        off = h[N: 2 * N + 1]
+        if self.compact:
+            for n in range(n_images):
+                if h[2 * N + 1 + n] > NMS_MAX_CANDIDATES:
+                    raise ValueError(f'image {n}: {int(h[2 * N + 1 + n])} candidate boxes exceed the NMS capacity of {NMS_MAX_CANDIDATES}; raise the score threshold')
+        sc = h[self._o_scores: self._o_scores + K].view('float32')
+        bb = h[self._o_bbox: self._o_bbox + 4 * K].view('float32').reshape(K, 4)
+        ci = h[self._o_cid: self._o_cid + K]
+        return [[sc[off[n]: off[n + 1]].copy(), bb[off[n]: off[n + 1]].copy(), ci[off[n]: off[n + 1]].copy()] for n in range(n_images)]
+
+    def __call__(self, conf, boxes, cand, iou_thr, n_images=None):
+        self.launch(conf, boxes, cand, iou_thr)
+        return self.read(n_images)
 
 
 def retina_detect(pconf, pbox, anchors_yx, anchors_hw, score_thr, max_boxes, iou_thr):

@@ -417,6 +417,46 @@ def ssd_decode(pred0, Cn, yx, hw, thr, conf, boxes, keep, cand):
          _p(cand), _stream())
 
 
+# ------------------------------------------------------------------ batched inference tail (csrc/detect_batched.hip)
+def ssd_decode_batched(pred, Cn, yx, hw, thr, conf, boxes, keep, cand):
+    """odtk_ssd_decode for N images in one launch: pred [N, A, ld] -> conf, cand [N, A, Cn-1], boxes [N, A, 4], keep [N, A]"""
+    N, A, ld = pred.shape
+    call("odtk_ssd_decode_batched", _p(pred), N, A, Cn, ld, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep), _p(cand), _stream())
+
+
+def retina_decode_batched(pconf, pbox, yx, hw, thr, conf, boxes, keep, cand):
+    """odtk_retina_decode for N images in one launch: pconf [N, A, C], pbox [N, A, 4] -> conf, cand [N, A, C-1], boxes [N, A, 4], keep [N, A]"""
+    N, A, Cn = pconf.shape
+    call("odtk_retina_decode_batched", _p(pconf), _p(pbox), N, A, Cn, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep), _p(cand), _stream())
+
+
+def nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, score_estride, valid, valid_istride, valid_cstride, valid_estride, valid_value,
+                    n, n_dev, N, num_classes, max_out, iou_thr, out_idx, cap, out_cnt):
+    """greedy NMS of N * num_classes problems (image x class) in one launch chain; operand addressing as in include/odtk.h"""
+    call("odtk_nms_image_class", _p(boxes), box_istride, _p(scores), score_istride, score_cstride, score_estride, _p(valid), valid_istride, valid_cstride,
+         valid_estride, valid_value, n, _p(n_dev), N, num_classes, int(max_out), float(iou_thr), _p(out_idx), cap, _p(out_cnt), _stream())
+
+
+def compact_rows(cand, num_classes, cap_rows, rows, counts):
+    """cand [N, A, ld] u8 -> rows [N, cap_rows] int32 (ascending indices of the rows with a candidate among the first num_classes columns), counts [N]"""
+    N, A, ld = cand.shape
+    call("odtk_compact_rows", _p(cand), N, A, ld, num_classes, cap_rows, _p(rows), _p(counts), _stream())
+
+
+def gather_rows(rows, counts, num_classes, conf, boxes, cand, conf_out, boxes_out, cand_out):
+    """the compacted rows of conf [N, A, ldc] / boxes [N, A, 4] / cand [N, A, ldk] -> [N, cap_rows, num_classes | 4 | num_classes]"""
+    N, A, ldc = conf.shape
+    call("odtk_gather_rows", _p(rows), _p(counts), N, A, rows.shape[1], num_classes, _p(conf), ldc, _p(boxes), _p(cand), cand.shape[2], _p(conf_out),
+         _p(boxes_out), _p(cand_out), _stream())
+
+
+def detection_pack(nms_idx, nms_cnt, conf, boxes, counts, offsets, scores, bbox, class_id):
+    """nms_idx [N, nc, cap], nms_cnt [N, nc], conf [N, n, ldc], boxes [N, n, 4] -> counts [N], offsets [N + 1], scores / bbox / class_id (room for N * nc * cap)"""
+    N, nc, cap = nms_idx.shape
+    call("odtk_detection_pack", _p(nms_idx), _p(nms_cnt), N, nc, cap, _p(conf), conf.shape[1] * conf.shape[2], conf.shape[2], _p(boxes), boxes.shape[1] * 4,
+         _p(counts), _p(offsets), _p(scores), _p(bbox), _p(class_id), _stream())
+
+
 # ------------------------------------------------------------------ RetinaNet box side (K16)
 def retina_anchors(input_dim, shapes, nas, prior_hw_flat, device):
     """shapes: [(fh, fw)] per level; returns (y1x1, y2x2, yx, hw) device tensors [A, 2]."""
@@ -600,13 +640,17 @@ def yolov2_decode_candidates(pred0, priors_flat, stride):
     return conf, bbox
 
 
-def yolov3_decode_candidates(preds, priors_flat, decode_scale):
-    """YOLOv3.py:320-350 for one image (three [H,W,P,C+5] tensors); returns confidence [L,C], bbox [L,4]."""
+def yolov3_decode_candidates(preds, priors_flat, decode_scale, out=None):
+    """YOLOv3.py:320-350 for one image (three [H,W,P,C+5] tensors); returns confidence [L,C], bbox [L,4] (written into `out` = (conf, bbox) when given)."""
     dev = preds[0].device
     P, E = preds[0].shape[-2], preds[0].shape[-1]
     L = sum(p.shape[0] * p.shape[1] * P for p in preds)
-    conf = torch.empty(L, E - 5, device=dev)
-    bbox = torch.empty(L, 4, device=dev)
+    if out is not None:
+        conf, bbox = out
+        assert tuple(conf.shape) == (L, E - 5) and tuple(bbox.shape) == (L, 4) and conf.is_contiguous() and bbox.is_contiguous()
+    else:
+        conf = torch.empty(L, E - 5, device=dev)
+        bbox = torch.empty(L, 4, device=dev)
     call("odtk_yolov3_decode_candidates", _ptr_array(preds), _yolo_shapes(preds), _farr(priors_flat), _farr(decode_scale), P, E - 5,
          _p(conf), _p(bbox), _stream())
     return conf, bbox

@@ -104,7 +104,7 @@ class RetinaNet(EvaluateMixin):
         self.weight_decay = config['weight_decay']
         self.data_format = config['data_format']
         self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
+        self.batch_size = config['batch_size'] if config['mode'] == 'train' else self._test_batch_size(config)
         self.gamma, self.alpha = config['gamma'], config['alpha']
         self.num_anchors = len(ASPECT_RATIOS) * len(ANCHOR_SCALES)
         self.nms_score_threshold = config['nms_score_threshold']
@@ -550,7 +550,31 @@ class RetinaNet(EvaluateMixin):
         return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
+    NATIVE_TEST_IMAGES = True
+    _tail_batched = None
+
+    def test_images(self, images):
+        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_retina_decode_batched -> (more anchors than the
+        NMS takes per problem: odtk_compact_rows + odtk_gather_rows, the place torch.nonzero holds in the single-image path) -> odtk_nms_image_class ->
+        odtk_detection_pack -> one read-back.  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
+        if self.is_pretraining:
+            raise ValueError("test_images: a classification pre-training model has no detections")
+        n = self._stage_test_images(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        N, A, nc = self.batch_size, self.pconf.shape[1], self.num_classes - 1
+        t = self._tail_batched
+        if t is None:
+            t = self._tail_batched = heads.BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
+            t.conf = torch.zeros(N, A, nc, device=self.dev)
+            t.boxes = torch.zeros(N, A, 4, device=self.dev)
+            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
+            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
+        ops.retina_decode_batched(self.pconf, self.pbox, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
+        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
+
     def test_one_image(self, images):
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self.test_images(images)[0]
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)

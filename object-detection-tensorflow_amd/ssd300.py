@@ -13,6 +13,7 @@ as torch tensors or numpy arrays -- exactly what utils/image_augmentor.py:24-27 
 
 Extra, optional config keys (absent in the reference): 'compute_dtype' ('bf16' | 'f32' | 'f32x3'; default bf16 in train mode, f32 in test mode),
 'device', 'seed', 'verbose', 'test_subtract_mean' (False = reproduce the reference's test-mode feed quirk),
+'test_batch_size' (test mode only, default 1: image slots of the test-mode buffers; test_images(images) runs up to that many images per forward pass),
 'use_graph' (False, default since round 3: eager launches -- measured 1-3 % FASTER than graph replay on every box once the step was down to ~200
 launches (profiles/r03e_launch_mode_ab.md) | True: replay the step's kernel launches from HIP graphs after two eager steps | 'auto' = the faster of the two,
 measured at start-up),
@@ -177,7 +178,7 @@ class SSD300(EvaluateMixin, F32Warmup):
         self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']                  # unused, as in the reference
         self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
+        self.batch_size = config['batch_size'] if config['mode'] == 'train' else self._test_batch_size(config)
         self.nms_score_threshold = config['nms_score_threshold']
         self.nms_max_boxes = config['nms_max_boxes']
         self.nms_iou_threshold = config['nms_iou_threshold']
@@ -1197,7 +1198,29 @@ class SSD300(EvaluateMixin, F32Warmup):
         return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
+    NATIVE_TEST_IMAGES = True
+    _tail_batched = None
+
+    def test_images(self, images):
+        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_ssd_decode_batched -> odtk_nms_image_class
+        (N x classes problems) -> odtk_detection_pack -> one read-back.  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
+        n = self._stage_test_images(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        N, A, nc = self.batch_size, self.NUM_PRIORS, self.num_classes - 1
+        t = self._tail_batched
+        if t is None:
+            from .heads import BatchedTail
+            t = self._tail_batched = BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
+            t.conf = torch.zeros(N, A, nc, device=self.dev)
+            t.boxes = torch.zeros(N, A, 4, device=self.dev)
+            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
+            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
+        ops.ssd_decode_batched(self.pred, self.num_classes, self.pri[2], self.pri[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
+        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
+
     def test_one_image(self, images):
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self.test_images(images)[0]
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)

@@ -126,10 +126,47 @@ def _batches(generator):
     return iter(iterator)
 
 
-def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='voc07'):
+def _chunks(generator, batch_size, num_images):
+    """the validation batches regrouped into (images [n, ...], ground_truth [n, pad, 5]) chunks of `batch_size` images, whatever the generator's own batch
+    is: the chunk that reaches `num_images` is cut short, the last chunk of the pass may be partial"""
+    pend_i, pend_g, have, left = [], [], 0, num_images
+
+    def flush(k):
+        nonlocal pend_i, pend_g, have
+        im = np.concatenate(pend_i) if len(pend_i) > 1 else pend_i[0]
+        if any(g.shape[1] != pend_g[0].shape[1] for g in pend_g):         # batches padded to different numbers of boxes: pad rows are cls -1
+            pad = max(g.shape[1] for g in pend_g)
+            pend_g = [np.concatenate([g, np.full((g.shape[0], pad - g.shape[1], 5), -1, g.dtype)], 1) for g in pend_g]
+        gt = np.concatenate(pend_g) if len(pend_g) > 1 else pend_g[0]
+        out = im[:k], gt[:k]
+        pend_i, pend_g, have = ([im[k:]], [gt[k:]], have - k) if have > k else ([], [], 0)
+        return out
+    for images, gt in _batches(generator):
+        images, gt = _host(images), _host(gt)
+        if left is not None:
+            if left <= have:
+                break
+            images, gt = images[: left - have], gt[: left - have]
+        if images.shape[0] == 0:
+            continue
+        pend_i.append(images); pend_g.append(gt); have += images.shape[0]
+        while have >= batch_size:
+            if left is not None:
+                left -= batch_size
+            yield flush(batch_size)
+    if have and (left is None or left > 0):
+        yield flush(have)
+
+
+def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='voc07', batch_size=1):
     """VOC mAP of `model` (test mode) over `generator`: batches (images [B, H, W, 3] or channels_first, ground_truth [B, pad, 5]) -- the
-    train_generator contract -- or an (initializer, iterator) pair.  Each batch is split into single images for model.test_one_image; stops after
-    `num_images` images or at the end of one pass.  Defaults: the model's val_generator and num_val (when > 0)."""
+    train_generator contract -- or an (initializer, iterator) pair.  batch_size 1 (default): each batch is split into single images for
+    model.test_one_image.  batch_size B > 1: the batches are regrouped into chunks of B images for model.test_images (the model must have been built with
+    test_batch_size >= B, or be one of the classes whose test_images is the documented loop).  Stops after `num_images` images or at the end of one pass.
+    Defaults: the model's val_generator and num_val (when > 0)."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"evaluate: batch_size must be >= 1, not {batch_size}")
     if generator is None:
         generator = getattr(model, 'val_generator', None)
         if generator is None:
@@ -143,6 +180,11 @@ def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='
             num_images = int(nv) if nv and int(nv) > 0 else None
     dev = getattr(model, 'dev', None)
     ev = VOCEvaluator(model.config['num_classes'], iou_threshold, metric, device=dev if dev is not None and dev.type == 'cuda' else None)
+    if batch_size > 1:
+        for images, gt in _chunks(generator, batch_size, num_images):
+            for det, g in zip(model.test_images(images), gt):
+                ev.add(det, g)
+        return ev.result()
     n = 0
     for images, gt in _batches(generator):
         images, gt = _host(images), _host(gt)
@@ -161,7 +203,45 @@ class EvaluateMixin:
     class once (config with mode 'test', no compute_dtype -> the class's inference default, no pretraining_weight -> nothing read from disk),
     copies the current weights and moving statistics into it (export_params -> load_oracle_params; mid-warm-up the live weights are the twin's)
     before each evaluation, and evaluates that: the training state -- parameters, optimizer state, global_step, a pending warm-up, captured
-    graphs -- is left as it was."""
+    graphs -- is left as it was.  `batch_size` B > 1 evaluates B images per forward pass through `test_images`; a train-mode model keeps one test-mode
+    copy per batch_size (built with test_batch_size = B) in `self._eval_models`; each copy holds its own weights and activation buffers at N = B on the
+    device until the entry is deleted (`del model._eval_models[B]`), so evaluate with ONE batch size per run rather than sweeping them.
+
+    `test_images(images)` here is the form every class has: a LOOP over `test_one_image`, NOT batched (FCOS, CenterNet, YOLOv2, RefineDet, PFPNetR,
+    Light-Head R-CNN).  SSD300, SSD512, YOLOv3 and RetinaNet override it with one forward pass at N = test_batch_size and the batched tail
+    (heads.BatchedTail)."""
+
+    NATIVE_TEST_IMAGES = False               # True in the classes whose test_images is one batched forward + tail
+
+    def test_images(self, images):
+        """images [n, H, W, 3] (or channels_first, as test_one_image accepts it) -> list of n [scores, bbox, class_id] triples, each exactly what
+        test_one_image returns for that image.  This form calls test_one_image n times: correct, uniform with the native classes, not batched."""
+        images = _host(images)
+        if images.ndim != 4 or images.shape[0] < 1:
+            raise ValueError(f"test_images: images must be [n, H, W, 3] (or channels_first) with n >= 1, not {tuple(images.shape)}")
+        return [self.test_one_image(images[b: b + 1]) for b in range(images.shape[0])]
+
+    def _stage_test_images(self, images):
+        """native classes: the n <= test_batch_size images into the first n slots of self.images (the tail slots keep what they held: computed, discarded)"""
+        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
+        if images.ndim == 4 and self.data_format == 'channels_first' and images.shape[1] == 3:
+            images = images.permute(0, 2, 3, 1)
+        if self.mode != 'test':
+            raise ValueError("test_images: the model was not built in test mode")
+        if images.ndim != 4 or not 1 <= images.shape[0] <= self.batch_size or tuple(images.shape[1:]) != tuple(self.images.shape[1:]):
+            raise ValueError(f"test_images: images must be [n, {', '.join(str(d) for d in self.images.shape[1:])}] with 1 <= n <= test_batch_size = "
+                             f"{self.batch_size}, not {tuple(images.shape)}")
+        n = images.shape[0]
+        self.images[:n].copy_(images)
+        return n
+
+    @staticmethod
+    def _test_batch_size(config):
+        """config['test_batch_size']: optional, an integer >= 1 (default 1), read in test mode only: the number of image slots of the test-mode buffers"""
+        b = config.get('test_batch_size', 1)
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
+            raise ValueError(f"test_batch_size must be an integer >= 1, not {b!r}")
+        return int(b)
 
     def evaluate(self, num_images=None, generator=None, **kw):
         if getattr(self, 'is_pretraining', False):
@@ -175,12 +255,23 @@ class EvaluateMixin:
             if num_images is None:
                 nv = getattr(self, 'num_val', 0)
                 num_images = int(nv) if nv and int(nv) > 0 else None
-        m = getattr(self, '_eval_model', None)
+        B = int(kw.get('batch_size', 1))
+        if B < 1:
+            raise ValueError(f"evaluate: batch_size must be >= 1, not {B}")
+        if not hasattr(self, '_eval_models'):
+            self._eval_models = {}
+        m = self._eval_models.get(B)
         if m is None:
             cfg = dict(self.config, mode='test')
             cfg.pop('compute_dtype', None)
             cfg['pretraining_weight'] = None
             cfg['device'] = self.dev
-            m = self._eval_model = type(self)(cfg, self.data_provider)
+            if B > 1 and self.NATIVE_TEST_IMAGES:
+                cfg['test_batch_size'] = B
+            else:
+                cfg.pop('test_batch_size', None)
+            m = self._eval_models[B] = type(self)(cfg, self.data_provider)
+            if B == 1:
+                self._eval_model = m
         m.load_oracle_params(self.export_params())
         return evaluate(m, generator, num_images, **kw)

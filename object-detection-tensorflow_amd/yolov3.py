@@ -64,7 +64,7 @@ class YOLOv3(EvaluateMixin, F32Warmup):
         self.weight_decay = config['weight_decay']
         self.data_format = config['data_format']
         self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
+        self.batch_size = config['batch_size'] if config['mode'] == 'train' else self._test_batch_size(config)
         self.scales = (config['coord_scale'], config['noobj_scale'], config['obj_scale'], config['class_scale'])
         self.num_priors = config['num_priors']
         self.nms_score_threshold = config['nms_score_threshold']
@@ -432,7 +432,32 @@ class YOLOv3(EvaluateMixin, F32Warmup):
         return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
+    NATIVE_TEST_IMAGES = True
+    _tail_batched = None
+
+    def test_images(self, images):
+        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail (heads.BatchedTail).  The decode is a LOOP of the
+        existing launch, odtk_yolov3_decode_candidates, one per image slot into [N, L, C] / [N, L, 4]: that entry point takes the three level tensors of an
+        image as a pointer table, a batched form would need a table per image, and the loop costs the host's enqueue time, measured 0.5 ms for 32 images (15 us per image, DESIGN.md *Evaluation*) beside a forward pass of 26 ms;
+        threshold, NMS (N x classes problems), pack and read-back are batched."""
+        n = self._stage_test_images(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        N, C_ = self.batch_size, self.num_classes
+        L = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in self.preds)
+        t = self._tail_batched
+        if t is None:
+            t = self._tail_batched = heads.BatchedTail(N, L, C_, self.nms_max_boxes, self.dev)
+            t.conf = torch.zeros(N, L, C_, device=self.dev)
+            t.boxes = torch.zeros(N, L, 4, device=self.dev)
+            t.cand = torch.zeros(N, L, C_, dtype=torch.bool, device=self.dev)
+        for b in range(N):
+            ops.yolov3_decode_candidates([p[b] for p in self.preds], self.priors_flat, (STRIDE[2], STRIDE[2], STRIDE[1]), out=(t.conf[b], t.boxes[b]))
+        torch.ge(t.conf, self.nms_score_threshold, out=t.cand)
+        return t(t.conf, t.boxes, t.cand.view(torch.uint8), self.nms_iou_threshold, n)
+
     def test_one_image(self, images):
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self.test_images(images)[0]
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)
