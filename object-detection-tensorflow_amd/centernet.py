@@ -23,14 +23,14 @@ from __future__ import annotations
 
 import math
 import os
-import sys
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
+from .base import DetectorBase
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
@@ -84,51 +84,24 @@ class _Act:
         self.g = None                                          # gradient buffer (train mode, allocated by _build_backward)
 
 
-class CenterNet(EvaluateMixin, F32Warmup):
-    OPT_BUFFERS = ('M1', 'M2')
+class CenterNet(EvaluateMixin, F32Warmup, DetectorBase):
+    OPT_BUFFERS = ('M1', 'M2')                                 # Adam's m and v
+    OPT_BLOB_KEYS = ('adam_m', 'adam_v')
+    PROGRESS_FROM = 1                                          # CenterNet.py's epoch loop prints i + 1
+
     def __init__(self, config, data_provider):
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider, nms=False)
         self.input_size = config['input_size']
         self.data_shape = [self.input_size, self.input_size, 3] if config['data_format'] == 'channels_last' else [3, self.input_size, self.input_size]
-        self.num_classes = config['num_classes']
-        self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']                   # unused, as in the reference
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
         assert self.input_size % 32 == 0, "CenterNet needs an input that is a multiple of 32 (five halvings; SAME pooling of odd maps is not implemented)"
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        else:
+        if self.mode == 'test':
             self.score_threshold = config['score_threshold']
             self.top_k_results_output = config['top_k_results_output']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
         # engine: bf16 by default on the GPU since round 3 (warmup.py: the first f32_warmup_steps optimizer steps of a run from random initialisation go through
         # an f32 twin); an explicit 'compute_dtype' is taken literally; the CPU stand-in of the library (host-logic tests) stays on f32
         # (mode 'test' keeps f32 unless asked otherwise, as ssd300.py does: the bf16 gate checks training gradients, not thresholded detections)
-        engine = config.get('compute_dtype', 'bf16' if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32')
-        # 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
-            torch.cuda.set_device(self.dev)
+        self._set_engine(config.get('compute_dtype', 'bf16' if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32'))
         self.specs = layer_specs(self.num_classes)
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
@@ -143,28 +116,20 @@ class CenterNet(EvaluateMixin, F32Warmup):
     def _init_parameters(self, seed):
         pinfo, sinfo = OrderedDict(), OrderedDict()
         off = soff = 0
-        self._kin = {}
+        self._cin = {}
         for spec in self.specs:
             name, cout = spec[0], spec[3]
             wshape, kin = self._wshape(spec)
-            self._kin[name] = kin
+            self._cin[name] = kin
             for suffix, shape in (('.w', wshape), ('.b', (cout,)), ('.gamma', (cout,)), ('.beta', (cout,))):
                 pinfo[name + suffix] = (off, shape)
                 off += ops.pad_to(int(np.prod(shape)), 64)
             for suffix in ('.mmean', '.mvar'):
                 sinfo[name + suffix] = (soff, (cout,))
                 soff += ops.pad_to(cout, 64)
-        self.pinfo, self.sinfo, self.nparam = pinfo, sinfo, off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.M1 = torch.zeros(off, device=dev)                 # Adam's m
-        self.M2 = torch.zeros(off, device=dev)                 # Adam's v
+        self.pinfo, self.sinfo = pinfo, sinfo
+        self._alloc_flat(off, soff)
         self.Mom = self.M1                                     # (name the data-parallel / checkpoint helpers of the other classes use)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.S = torch.zeros(soff, device=dev)
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
         g = torch.Generator().manual_seed(seed)
         for name, kind, cin, cout, k, _, _, _ in self.specs:
             kout, kin = (cout, cin) if kind == 'conv' else (cin, cout)
@@ -172,59 +137,10 @@ class CenterNet(EvaluateMixin, F32Warmup):
             self.param(name + '.gamma').fill_(1.0)
             self.stat(name + '.mvar').fill_(1.0)
 
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def stat(self, name):
-        off, shape = self.sinfo[name]
-        return self.S[off: off + int(np.prod(shape))].view(shape)
-
-    def _flat(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
-    def set_param(self, name, value):
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self._kin[name[:-2]]].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        for k, v in p.items():
-            if k in self.pinfo:
-                if k.endswith('.b') and self._layer_kind[k[:-2]] == 'dconv' and float(torch.as_tensor(v).abs().max()) != 0.0:
-                    raise NotImplementedError('non-zero bias of a transposed convolution (TensorFlow initialises it to 0 and, in front of a '
-                                              'batch norm, neither the loss gradient nor the weight decay ever moves it)')
-                self.set_param(k, v)
-            elif k in self.sinfo:
-                self.stat(k).copy_(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        self._sync_from_twin()
-        out = OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-        for k in self.sinfo:
-            out[k] = self.stat(k).detach().cpu().clone()
-        return out
-
-    def _refresh_operand_copies(self):
-        if self.DT == BF16:
-            ops.cast_from_f32(self.P, self.Pc)
-        if getattr(self, '_fp_batch', None) is not None:
-            self._fp_batch.run()
+    def _check_oracle_param(self, k, v):
+        if k.endswith('.b') and self._layer_kind[k[:-2]] == 'dconv' and float(torch.as_tensor(v).abs().max()) != 0.0:
+            raise NotImplementedError('non-zero bias of a transposed convolution (TensorFlow initialises it to 0 and, in front of a '
+                                      'batch norm, neither the loss gradient nor the weight decay ever moves it)')
 
     # ------------------------------------------------------------------ the graph: buffers + launch plan
     def _build(self):
@@ -459,17 +375,6 @@ class CenterNet(EvaluateMixin, F32Warmup):
                 self._fold(x, acc)
 
     # ------------------------------------------------------------------ public: training
-    def _set_batch_engine(self, images, ground_truth):
-        images = torch.as_tensor(images, dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images, non_blocking=True)
-        gt = torch.as_tensor(ground_truth, dtype=torch.float32)
-        if self.gt is None or self.gt.shape != gt.shape:
-            self.gt = torch.zeros(gt.shape, device=self.dev)
-        self.gt.copy_(gt, non_blocking=True)
-
     def _train_step_engine(self, lr):
         """one AdamOptimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
         if self.dist is not None:
@@ -491,28 +396,6 @@ class CenterNet(EvaluateMixin, F32Warmup):
         self._fp_batch.run()
         return self.loss_parts[:, 3].mean() + self.weight_decay * self.l2_sum          # CenterNet.py:152-153 (pre-update weights)
 
-    def train_one_epoch(self, lr):
-        if callable(self.train_initializer):
-            self.train_initializer()
-        mean_loss = []
-        num_iters = self.num_train // self.batch_size
-        it = iter(self.train_iterator)
-        for i in range(num_iters):
-            try:
-                images, gt = next(it)
-            except StopIteration:
-                it = iter(self.train_iterator)
-                images, gt = next(it)
-            self.set_batch(images, gt)
-            loss = float(self.train_step(lr).item())
-            if self.verbose:
-                sys.stdout.write('\r>> ' + 'iters ' + str(i + 1) + str('/') + str(num_iters) + ' loss ' + str(loss))
-                sys.stdout.flush()
-            mean_loss.append(loss)
-        if self.verbose:
-            sys.stdout.write('\n')
-        return np.mean(mean_loss)
-
     # ------------------------------------------------------------------ public: inference
     def test_one_image(self, images):
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
@@ -528,11 +411,6 @@ class CenterNet(EvaluateMixin, F32Warmup):
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def _logical(self, name, buf):
-        """parameter `name` out of a flat buffer in TensorFlow's layout: kernels HWIO (transposed convs [h, w, out, in]), un-padded"""
-        v = self.get_param(name, buf)
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
-
     def export_tf_variables(self):
         """what the reference's `tf.train.Saver()` (CenterNet.py:296-301) would write: weights, moving statistics, global_step and AdamOptimizer's state --
         slots `center_detector/<variable>/Adam` (m), `…/Adam_1` (v) and the accumulators `center_detector/beta1_power` / `beta2_power`
@@ -575,13 +453,7 @@ class CenterNet(EvaluateMixin, F32Warmup):
                         missing_slots.append(tfname + slot)
                     else:
                         mv = torch.from_numpy(reader.get_tensor(found[0]))
-                        dst = self.param(ours, buf)
-                        if ours.endswith('.w'):
-                            mv = mv.permute(3, 0, 1, 2)
-                            dst.zero_()
-                            dst[..., : mv.shape[-1]] = mv.to(self.dev)
-                        else:
-                            dst.copy_(mv.to(self.dev).view(dst.shape))
+                        self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, buf)
             else:
                 self.stat(ours).copy_(v.to(self.dev))
         if not backbone_only and reader.has_tensor('global_step'):
@@ -591,26 +463,6 @@ class CenterNet(EvaluateMixin, F32Warmup):
             warnings.warn(f'{path}: {len(missing_slots)} Adam slot variables not in the checkpoint (e.g. {missing_slots[0]}): their moments stay as they are, '
                           f'while global_step = {self.global_step} drives the bias correction', RuntimeWarning)
         self._refresh_operand_copies()
-
-    def _save_weight_engine(self, mode, path):
-        """CenterNet.py:314-319: one torch file `<path>-<step>` (parameters, moving statistics, Adam's moments and step), or with
-        config['checkpoint_format'] = 'tf' the reference's own tf.train.Saver files"""
-        assert (mode in ['latest', 'best'])
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        if self.config.get('checkpoint_format', 'torch') == 'tf':
-            from . import tf_checkpoint
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        blob = {'params': self.export_params(), 'adam_m': self.M1.detach().cpu(), 'adam_v': self.M2.detach().cpu(), 'global_step': self.global_step,
-                'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
 
     def load_weight(self, path):
         if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
@@ -637,12 +489,6 @@ class CenterNet(EvaluateMixin, F32Warmup):
         blob = torch.load(path, map_location='cpu', weights_only=True)['params']
         self.load_oracle_params({k: v for k, v in blob.items() if k in self.pinfo and int(k[1:].split('.')[0]) < 50})
         print('load pretrained weight', path, 'successfully')
-
-    def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
-        from .dist import GradAllReducer
-        self.dist = GradAllReducer(self, group, bucket_mb, grad_dtype, force_collectives, collective)
-        self.loss_divisor_batch = self.batch_size * self.dist.world
-        return self.dist
 
 
 def reference_variable_map(num_classes=20):

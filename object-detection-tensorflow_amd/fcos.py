@@ -19,14 +19,14 @@ from __future__ import annotations
 
 import math
 import os
-import sys
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
+from .base import DetectorBase, _Act
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
@@ -78,55 +78,14 @@ def layer_specs(num_classes):
 HEAD_LAYERS = 11                                               # the last 11 specs: 6 classifier-head + 5 regress-head layers, shared by the levels
 
 
-class _Act:
-    def __init__(self, name, N, H, W, C, ld, dtype, dev):
-        self.name, self.N, self.H, self.W, self.C, self.ld = name, N, H, W, C, ld
-        self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev)
-        self.gid = name
-
-
-class FCOS(EvaluateMixin, F32Warmup):
+class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
     def __init__(self, config, data_provider):
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider)
         self.data_shape = config['data_shape']
-        self.num_classes = config['num_classes']
-        self.weight_decay = config['weight_decay']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
         # engine: bf16 by default on the GPU since round 3 (warmup.py: the first f32_warmup_steps optimizer steps of a run from random initialisation go through
         # an f32 twin); an explicit 'compute_dtype' is taken literally; the CPU stand-in of the library (host-logic tests) stays on f32
         # (mode 'test' keeps f32 unless asked otherwise, as ssd300.py does: the bf16 gate checks training gradients, not thresholded detections)
-        engine = config.get('compute_dtype', 'bf16' if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32')
-        # 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
-            torch.cuda.set_device(self.dev)
+        self._set_engine(config.get('compute_dtype', 'bf16' if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32'))
         self.specs = layer_specs(self.num_classes)
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
@@ -144,62 +103,13 @@ class FCOS(EvaluateMixin, F32Warmup):
 
     def _init_parameters(self, seed):
         self.pinfo, off = self.param_layout()
-        self.nparam = off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.Mom = torch.zeros(off, device=dev)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
+        self._alloc_flat(off)
         self._cin = {s[0]: s[1] for s in self.specs}
         g = torch.Generator().manual_seed(seed)
         for name, cin, cout, k, _, _, bias_init in self.specs:
             self.set_param(name + '.w', torch.randn(cout, k, k, cin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
             self.param(name + '.b').fill_(float(bias_init))
             self.param(name + '.gamma').fill_(1.0)
-
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def _flat(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
-    def set_param(self, name, value):
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self._cin[name[:-2]]].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        for k, v in p.items():
-            if k in self.pinfo:
-                self.set_param(k, v)
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        self._sync_from_twin()
-        return OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-
-    def _refresh_operand_copies(self):
-        if self.DT == BF16:
-            ops.cast_from_f32(self.P, self.Pc)
-        if getattr(self, '_fp_batch', None) is not None:
-            self._fp_batch.run()
 
     # ------------------------------------------------------------------ the graph
     def _build(self):
@@ -431,17 +341,6 @@ class FCOS(EvaluateMixin, F32Warmup):
                 yield name
 
     # ------------------------------------------------------------------ public: training
-    def _set_batch_engine(self, images, ground_truth):
-        images = torch.as_tensor(images, dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images, non_blocking=True)
-        gt = torch.as_tensor(ground_truth, dtype=torch.float32)
-        if self.gt is None or self.gt.shape != gt.shape:
-            self.gt = torch.zeros(gt.shape, device=self.dev)
-        self.gt.copy_(gt, non_blocking=True)
-
     def _train_step_engine(self, lr):
         """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
         if self.dist is not None:
@@ -460,28 +359,6 @@ class FCOS(EvaluateMixin, F32Warmup):
         self.global_step += 1
         return self.loss_img.mean() + self.weight_decay * self.l2_sum                              # FCOS.py:186-187
 
-    def train_one_epoch(self, lr):
-        if callable(self.train_initializer):
-            self.train_initializer()
-        mean_loss = []
-        num_iters = self.num_train // self.batch_size
-        it = iter(self.train_iterator)
-        for i in range(num_iters):
-            try:
-                images, gt = next(it)
-            except StopIteration:
-                it = iter(self.train_iterator)
-                images, gt = next(it)
-            self.set_batch(images, gt)
-            loss = float(self.train_step(lr).item())
-            if self.verbose:
-                sys.stdout.write('\r>> ' + 'iters ' + str(i) + str('/') + str(num_iters) + ' loss ' + str(loss))
-                sys.stdout.flush()
-            mean_loss.append(loss)
-        if self.verbose:
-            sys.stdout.write('\n')
-        return np.mean(mean_loss)
-
     # ------------------------------------------------------------------ public: inference
     def test_one_image(self, images):
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
@@ -495,10 +372,6 @@ class FCOS(EvaluateMixin, F32Warmup):
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def _logical(self, name, buf):
-        v = self.get_param(name, buf)
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
-
     def export_tf_variables(self):
         """what the reference's `tf.train.Saver()` (FCOS.py:390-394) writes: every variable under its name (reference_variable_map),
         global_step, and the momentum slots `<variable>/Momentum` created under the 'head' scope of the graph (:111, :188)"""
@@ -524,53 +397,10 @@ class FCOS(EvaluateMixin, F32Warmup):
             slot = [k for k in names if k.endswith(tfname + '/Momentum')]
             if slot and not backbone_only:
                 mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                dst = self.param(ours, self.Mom)
-                if ours.endswith('.w'):
-                    dst.zero_()
-                    dst[..., : mv.shape[2]] = mv.permute(3, 0, 1, 2).to(self.dev)
-                else:
-                    dst.copy_(mv.to(self.dev).view(dst.shape))
+                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
         if not backbone_only and reader.has_tensor('global_step'):
             self.global_step = int(reader.get_tensor('global_step'))
         self._refresh_operand_copies()
-
-    def _save_weight_engine(self, mode, path):
-        """FCOS.py:418-428.  config['checkpoint_format'] = 'tf' writes tf.train.Saver files (tf_checkpoint.py)."""
-        assert (mode in ['latest', 'best'])
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        if self.config.get('checkpoint_format', 'torch') == 'tf':
-            from . import tf_checkpoint
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        blob = {'params': self.export_params(), 'momentum': self.Mom.detach().cpu(), 'global_step': self.global_step, 'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        unknown = sorted(k for k in blob['params'] if k not in self.pinfo and k not in getattr(self, 'sinfo', {}))
-        if unknown:
-            raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
-                             'it was written by a different layer layout')
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
 
     def load_pretrained_weight(self, path):
         """FCOS.py:434-436 restores the 'backone' variables: here the stem + unit layers of a saved file"""
@@ -582,12 +412,6 @@ class FCOS(EvaluateMixin, F32Warmup):
         nb = 1 + 4 * sum(BLOCKS)
         self.load_oracle_params({k: v for k, v in blob.items() if int(k[1:].split('.')[0]) < nb})
         print('load pretrained weight', path, 'successfully')
-
-    def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
-        from .dist import GradAllReducer
-        self.dist = GradAllReducer(self, group, bucket_mb, grad_dtype, force_collectives, collective)
-        self.loss_divisor_batch = self.batch_size * self.dist.world
-        return self.dist
 
 
 def reference_variable_map():

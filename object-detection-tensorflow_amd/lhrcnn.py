@@ -452,13 +452,7 @@ class LHRCNN(RefineDet320):
                 self.set_param(ours, self._from_tf(ours, reader.get_tensor(tfname)))      # KeyError = Saver's NotFoundError
                 slot = [k for k in names if k.endswith(tfname + '/Momentum')]
                 if slot:
-                    mv = self._from_tf(ours, reader.get_tensor(slot[0]))
-                    dst = self.param(ours, self.Mom)
-                    if ours.endswith('.w'):
-                        dst.zero_()
-                        dst[..., : mv.shape[-1]] = mv.to(self.dev)
-                    else:
-                        dst.copy_(mv.to(self.dev).view(dst.shape))
+                    self.set_param(ours, self._from_tf(ours, reader.get_tensor(slot[0])), self.Mom)
             else:
                 self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
         if reader.has_tensor('global_step'):

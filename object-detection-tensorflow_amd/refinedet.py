@@ -20,14 +20,14 @@ from __future__ import annotations
 
 import math
 import os
-import sys
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
+from .base import DetectorBase
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
@@ -77,7 +77,7 @@ class _Act:
         self.g = None
 
 
-class RefineDet320(EvaluateMixin, F32Warmup):
+class RefineDet320(EvaluateMixin, F32Warmup, DetectorBase):
     # RefineDet320 / PFPNetR do not pass the bf16 gate (one head layer loses its direction); YOLOv2 does.  Round 4: their default is the f32 engine with
     # ODTK_F32X3 convolution descriptors (three bf16 MFMA products per f32 product): it passes the same gate at RANDOM INITIALISATION (minimum cosine 0.998 / 0.999
     # against the exact f32 engine) at 2.1x the exact engine's throughput (607 / 598 against 282 / 286 images/s)
@@ -85,54 +85,23 @@ class RefineDet320(EvaluateMixin, F32Warmup):
     VGG_SEQ = VGG_SEQ                       # the trunk this class builds (pfpnet.PFPNetR stops at conv4_3)
     L2_AFTER = 'conv10_2'                   # creation order: the two L2-norm scalars follow the feature extractor (:77, :79)
     NAME = 'RefineDet'
+    PROGRESS_FROM = 1                       # RefineDet.py's epoch loop prints i + 1
 
     @staticmethod
     def layer_specs(num_classes):
         return layer_specs(num_classes)
 
     def __init__(self, config, data_provider):
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider)
         self.input_size = config['input_size']
         self.data_shape = [self.input_size, self.input_size, 3] if config['data_format'] == 'channels_last' else [3, self.input_size, self.input_size]
         self.num_classes = config['num_classes'] + 1          # background = LAST index
-        self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
         self.anchor_ratios = [0.5, 1.0, 2.0]
         self.num_anchors = NA
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
         self.pretraining_weight = config.get('pretraining_weight')
         assert self.input_size % 64 == 0, f"{self.NAME}: the input size must be a multiple of 64 (320 or 512 in the reference)"
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
-        engine = config.get('compute_dtype', self.DEFAULT_ENGINE if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32')
-        # 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':
-            torch.cuda.set_device(self.dev)
+        self._set_engine(config.get('compute_dtype', self.DEFAULT_ENGINE if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32'))
         self.specs = self.layer_specs(self.num_classes)
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
@@ -151,7 +120,7 @@ class RefineDet320(EvaluateMixin, F32Warmup):
     def _init_parameters(self, seed):
         pinfo, sinfo = OrderedDict(), OrderedDict()
         off = soff = 0
-        self._kin, self._kind = {}, {}
+        self._cin, self._kind = {}, {}
 
         def add(name, shape):
             nonlocal off
@@ -160,7 +129,7 @@ class RefineDet320(EvaluateMixin, F32Warmup):
         for i, spec in enumerate(self.specs):
             name, kind, cout = spec[0], spec[1], spec[3]
             wshape, kin = self._wshape(spec)
-            self._kin[name], self._kind[name] = kin, kind
+            self._cin[name], self._kind[name] = kin, kind
             for extra, shape in self._extra_layer_params(spec):       # e.g. the depthwise filter of a separable layer (lhrcnn.LHRCNN), created first
                 add(extra, shape)
             add(name + '.w', wshape); add(name + '.b', (cout,))
@@ -171,15 +140,8 @@ class RefineDet320(EvaluateMixin, F32Warmup):
                     soff += ops.pad_to(cout, 64)
             if name == self.L2_AFTER:
                 add('feat1_l2_norm', (1,)); add('feat2_l2_norm', (1,))
-        self.pinfo, self.sinfo, self.nparam = pinfo, sinfo, off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.Mom = torch.zeros(off, device=dev)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.S = torch.zeros(soff, device=dev)
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
+        self.pinfo, self.sinfo = pinfo, sinfo
+        self._alloc_flat(off, soff)
         g = torch.Generator().manual_seed(seed)
         for name, kind, cin, cout, k, _, _, _ in self.specs:
             kout, kin = (cout, cin) if kind != 'dconv' else (cin, cout)
@@ -191,58 +153,9 @@ class RefineDet320(EvaluateMixin, F32Warmup):
             self.param('feat1_l2_norm').fill_(10.0)
             self.param('feat2_l2_norm').fill_(8.0)
 
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def stat(self, name):
-        off, shape = self.sinfo[name]
-        return self.S[off: off + int(np.prod(shape))].view(shape)
-
-    def _flat(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
-    def set_param(self, name, value):
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self._kin[name[:-2]]].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        for k, v in p.items():
-            if k in self.pinfo:
-                if k.endswith('.b') and self._kind.get(k[:-2]) == 'dconv' and float(torch.as_tensor(v).abs().max()) != 0.0:
-                    raise NotImplementedError('non-zero bias of a transposed convolution (zero-initialised, in front of a batch norm: it never moves)')
-                self.set_param(k, v)
-            elif k in self.sinfo:
-                self.stat(k).copy_(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        self._sync_from_twin()
-        out = OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-        for k in self.sinfo:
-            out[k] = self.stat(k).detach().cpu().clone()
-        return out
-
-    def _refresh_operand_copies(self):
-        if self.DT == BF16:
-            ops.cast_from_f32(self.P, self.Pc)
-        if getattr(self, '_fp_batch', None) is not None:
-            self._fp_batch.run()
+    def _check_oracle_param(self, k, v):
+        if k.endswith('.b') and self._kind.get(k[:-2]) == 'dconv' and float(torch.as_tensor(v).abs().max()) != 0.0:
+            raise NotImplementedError('non-zero bias of a transposed convolution (zero-initialised, in front of a batch norm: it never moves)')
 
     def _load_pretraining_weight(self):
         """the 13 VGG convolutions from slim's vgg_16.ckpt (RefineDet.py:33, :232-365), as ssd300.py does"""
@@ -627,17 +540,8 @@ class RefineDet320(EvaluateMixin, F32Warmup):
                 ops.relu_bwd(y.t, y.g, y.ld, b.g, b.ld, y.M, y.ld, acc_b)
 
     # ------------------------------------------------------------------ public: training
-    def _set_batch_engine(self, images, ground_truth):
-        images = torch.as_tensor(images, dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images, non_blocking=True)
-        gt = torch.as_tensor(ground_truth, dtype=torch.float32)
-        if self.gt is None or self.gt.shape != gt.shape:
-            self.gt = torch.zeros(gt.shape, device=self.dev)
-            self.loss = self._make_loss(gt.shape[1])
-        self.gt.copy_(gt, non_blocking=True)
+    def _gt_reshaped(self, shape):
+        self.loss = self._make_loss(shape[1])
 
     def _make_loss(self, pad):
         return heads.RefineDetLoss(self.anc, self.batch_size, self.num_classes, pad, self.dev)
@@ -682,28 +586,6 @@ class RefineDet320(EvaluateMixin, F32Warmup):
         self._fp_batch.run()
         self.global_step += 1
         return self._data_loss + self.weight_decay * self.l2_sum      # RefineDet.py:180-184 (pre-update weights)
-
-    def train_one_epoch(self, lr):
-        if callable(self.train_initializer):
-            self.train_initializer()
-        mean_loss = []
-        num_iters = self.num_train // self.batch_size
-        it = iter(self.train_iterator)
-        for i in range(num_iters):
-            try:
-                images, gt = next(it)
-            except StopIteration:
-                it = iter(self.train_iterator)
-                images, gt = next(it)
-            self.set_batch(images, gt)
-            loss = float(self.train_step(lr).item())
-            if self.verbose:
-                sys.stdout.write('\r>> ' + 'iters ' + str(i + 1) + str('/') + str(num_iters) + ' loss ' + str(loss))
-                sys.stdout.flush()
-            mean_loss.append(loss)
-        if self.verbose:
-            sys.stdout.write('\n')
-        return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
     def test_one_image(self, images):
@@ -754,11 +636,6 @@ class RefineDet320(EvaluateMixin, F32Warmup):
                 out[k] = 'feature_extractor/' + k
         return out
 
-    def _logical(self, name, buf):
-        """parameter `name` out of a flat buffer (P or Mom) in TensorFlow's layout: kernels HWIO (transposed convs: [h, w, out, in]), un-padded"""
-        v = self.get_param(name, buf)
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
-
     def export_tf_variables(self):
         """what the reference's `tf.train.Saver()` would write: every global variable -- weights, moving statistics, global_step and the MomentumOptimizer slots"""
         self._sync_from_twin()
@@ -786,65 +663,9 @@ class RefineDet320(EvaluateMixin, F32Warmup):
                 slot = [k for k in names if k.endswith(tfname + '/Momentum')]
                 if slot:
                     mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                    dst = self.param(ours, self.Mom)
-                    if ours.endswith('.w'):
-                        mv = mv.permute(3, 0, 1, 2)
-                        dst.zero_()
-                        dst[..., : mv.shape[-1]] = mv.to(self.dev)
-                    else:
-                        dst.copy_(mv.to(self.dev).view(dst.shape))
+                    self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
             else:
                 self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
         if reader.has_tensor('global_step'):
             self.global_step = int(reader.get_tensor('global_step'))
         self._refresh_operand_copies()
-
-    def _save_weight_engine(self, mode, path):
-        """config['checkpoint_format'] = 'tf' writes the reference's own files (`<path>-<step>.index` + `.data-00000-of-00001` + `checkpoint`, readable by its
-        `load_weight`); the default keeps one torch file `<path>-<step>`."""
-        assert (mode in ['latest', 'best'])
-        if self.config.get('checkpoint_format', 'torch') == 'tf':
-            from . import tf_checkpoint
-            dirname = os.path.dirname(path)
-            if dirname and not os.path.exists(dirname):
-                os.makedirs(dirname)
-                print(dirname, 'does not exist, create it done')
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        blob = {'params': self.export_params(), 'momentum': self.Mom.detach().cpu(), 'global_step': self.global_step,
-                'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        unknown = sorted(k for k in blob['params'] if k not in self.pinfo and k not in getattr(self, 'sinfo', {}))
-        if unknown:
-            raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
-                             'it was written by a different layer layout')
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
-
-    def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
-        from .dist import GradAllReducer
-        self.dist = GradAllReducer(self, group, bucket_mb, grad_dtype, force_collectives, collective)
-        self.loss_divisor_batch = self.batch_size * self.dist.world
-        return self.dist

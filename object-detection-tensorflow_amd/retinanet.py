@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
+from .base import DetectorBase, _Act
 from .voc_eval import EvaluateMixin
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -81,37 +82,17 @@ def level_priors(size):
     return out
 
 
-class _Act:
-    def __init__(self, name, N, H, W, C, ld, dtype, dev):
-        self.name, self.N, self.H, self.W, self.C, self.ld = name, N, H, W, C, ld
-        self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev)
-        self.gid = name
-
-
-class RetinaNet(EvaluateMixin):
+class RetinaNet(EvaluateMixin, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
         self.is_pretraining = bool(config.get('is_pretraining'))
         assert config['is_bottleneck'], 'only the bottleneck units of testretinanet.py are built'
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider, native_test_batch=True)
         self.block_list = list(config['residual_block_list'])
         self.data_shape = config['data_shape']
         self.num_classes = config['num_classes'] + 1
-        self.weight_decay = config['weight_decay']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else self._test_batch_size(config)
         self.gamma, self.alpha = config['gamma'], config['alpha']
         self.num_anchors = len(ASPECT_RATIOS) * len(ANCHOR_SCALES)
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
         # f32 by default: the reference's identity-free residual units amplify bf16's rounding of the stored activations to O(1) by the
         # end of the backbone at random initialisation; 'bf16' runs (3.4x faster) but is not validated for training
         # 'f32x3' (round 4): the f32 engine -- every tensor stays f32 -- whose convolution DESCRIPTORS say ODTK_F32X3: the library runs a layer's three passes as
@@ -121,25 +102,7 @@ class RetinaNet(EvaluateMixin):
         # f32 engine's throughput; mode 'test' keeps the exact 'f32'.
         engine = config.get('compute_dtype') or ('f32x3' if config['mode'] == 'train' else 'f32')
         self.x3 = engine == 'f32x3'
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if self.x3 else self.DT             # what the convolution descriptors carry
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
-            torch.cuda.set_device(self.dev)
+        self._set_engine(engine)
         self.specs = layer_specs(self.block_list, config['init_conv_filters'], self.num_classes, self.num_anchors)
         if self.is_pretraining:                     # the backbone alone: stem + units (RetinaNet.py:120-122)
             self.specs = self.specs[: 1 + 4 * sum(self.block_list)]
@@ -166,15 +129,7 @@ class RetinaNet(EvaluateMixin):
 
     def _init_parameters(self, seed):
         self.pinfo, off, self.sinfo, soff = self.param_layout()
-        self.nparam = off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.Mom = torch.zeros(off, device=dev)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.S = torch.zeros(soff, device=dev)
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
+        self._alloc_flat(off, soff)
         self._cin = {s[0]: s[1] for s in self.specs}
         g = torch.Generator().manual_seed(seed)
         for name, cin, cout, k, _, _, bias_init in self.specs:
@@ -182,54 +137,6 @@ class RetinaNet(EvaluateMixin):
             self.param(name + '.b').fill_(float(bias_init))
             self.param(name + '.gamma').fill_(1.0)
             self.stat(name + '.mvar').fill_(1.0)
-
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def stat(self, name):
-        off, shape = self.sinfo[name]
-        return self.S[off: off + int(np.prod(shape))].view(shape)
-
-    def _flat(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
-    def set_param(self, name, value):
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self._cin[name[:-2]]].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        for k, v in p.items():
-            if k in self.pinfo:
-                self.set_param(k, v)
-            elif k in self.sinfo:
-                self.stat(k).copy_(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        out = OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-        for k in self.sinfo:
-            out[k] = self.stat(k).detach().cpu().clone()
-        return out
-
-    def _refresh_operand_copies(self):
-        if self.DT == BF16:
-            ops.cast_from_f32(self.P, self.Pc)
-        if getattr(self, '_fp_batch', None) is not None:
-            self._fp_batch.run()
 
     # ------------------------------------------------------------------ the graph
     def _build(self):
@@ -497,15 +404,7 @@ class RetinaNet(EvaluateMixin):
     def set_batch(self, images, ground_truth):
         if self.is_pretraining:                     # (images, labels)
             return self._set_pretraining_batch(images, ground_truth)
-        images = torch.as_tensor(images, dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images, non_blocking=True)
-        gt = torch.as_tensor(ground_truth, dtype=torch.float32)
-        if self.gt is None or self.gt.shape != gt.shape:
-            self.gt = torch.zeros(gt.shape, device=self.dev)
-        self.gt.copy_(gt, non_blocking=True)
+        self._set_batch_engine(images, ground_truth)
 
     def train_step(self, lr):
         """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
@@ -526,28 +425,6 @@ class RetinaNet(EvaluateMixin):
         self._fp_batch.run()
         self.global_step += 1
         return self.loss_parts.sum() / self.batch_size + self.weight_decay * self.l2_sum          # RetinaNet.py:205-213
-
-    def train_one_epoch(self, lr):
-        if callable(self.train_initializer):
-            self.train_initializer()
-        mean_loss = []
-        num_iters = self.num_train // self.batch_size
-        it = iter(self.train_iterator)
-        for i in range(num_iters):
-            try:
-                images, gt = next(it)
-            except StopIteration:
-                it = iter(self.train_iterator)
-                images, gt = next(it)
-            self.set_batch(images, gt)
-            loss = float(self.train_step(lr).item())
-            if self.verbose:
-                sys.stdout.write('\r>> ' + 'iters ' + str(i) + str('/') + str(num_iters) + ' loss ' + str(loss))
-                sys.stdout.flush()
-            mean_loss.append(loss)
-        if self.verbose:
-            sys.stdout.write('\n')
-        return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
     NATIVE_TEST_IMAGES = True
@@ -586,10 +463,6 @@ class RetinaNet(EvaluateMixin):
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def _logical(self, name, buf):
-        v = self.get_param(name, buf)
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
-
     def export_tf_variables(self):
         """what the reference's detection `tf.train.Saver()` (RetinaNet.py:553-557) writes: every variable of the graph under its name
         (reference_variable_map), global_step, and the momentum slots, created inside the 'inference' scope (:172, :206)"""
@@ -621,53 +494,14 @@ class RetinaNet(EvaluateMixin):
             slot = [k for k in names if k.endswith(tfname + '/Momentum')]
             if slot and not backbone_only:
                 mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                dst = self.param(ours, self.Mom)
-                if ours.endswith('.w'):
-                    dst.zero_()
-                    dst[..., : mv.shape[2]] = mv.permute(3, 0, 1, 2).to(self.dev)
-                else:
-                    dst.copy_(mv.to(self.dev).view(dst.shape))
+                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
         if not backbone_only and reader.has_tensor('global_step'):
             self.global_step = int(reader.get_tensor('global_step'))
         self._refresh_operand_copies()
 
     def save_weight(self, mode, path):
         """RetinaNet.py:521-531.  config['checkpoint_format'] = 'tf' writes tf.train.Saver files (tf_checkpoint.py)."""
-        assert (mode in ['latest', 'best'])
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        if self.config.get('checkpoint_format', 'torch') == 'tf':
-            from . import tf_checkpoint
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        blob = {'params': self.export_params(), 'momentum': self.Mom.detach().cpu(), 'global_step': self.global_step, 'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        unknown = sorted(k for k in blob['params'] if k not in self.pinfo and k not in getattr(self, 'sinfo', {}))
-        if unknown:
-            raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
-                             'it was written by a different layer layout')
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
+        return self._save_weight_engine(mode, path)
 
     def load_pretraining_weight(self, path):
         """RetinaNet.py:537-539 restores the 'feature_extractor' variables saved by the pre-training graph: here the backbone layers
@@ -684,10 +518,7 @@ class RetinaNet(EvaluateMixin):
     def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
         if self.is_pretraining:
             raise NotImplementedError('data-parallel training of the classification pre-training graph is not built yet: run it on one device')
-        from .dist import GradAllReducer
-        self.dist = GradAllReducer(self, group, bucket_mb, grad_dtype, force_collectives, collective)
-        self.loss_divisor_batch = self.batch_size * self.dist.world
-        return self.dist
+        return super().attach_data_parallel(group, bucket_mb, grad_dtype, force_collectives, collective)
 
     # ------------------------------------------------------------------ classification pre-training (is_pretraining: True)
     def _build_pretraining(self, feat, it):

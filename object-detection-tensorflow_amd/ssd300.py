@@ -32,6 +32,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import BF16, F32, F32X3
+from .base import DetectorBase
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
@@ -144,7 +145,7 @@ class _Conv:
         self.bn, self.relu = bn, relu
 
 
-class SSD300(EvaluateMixin, F32Warmup):
+class SSD300(EvaluateMixin, F32Warmup, DetectorBase):
     # the variant: SSD512 (ssd512.py) overrides these
     INPUT_SIZE = INPUT_SIZE
     FEATURE_SIZES = FEATURE_SIZES
@@ -223,7 +224,6 @@ class SSD300(EvaluateMixin, F32Warmup):
                 self.val_generator = data_provider['val_generator']
         self.global_step = 0
         self.sync_bn = None
-        self.checkpoint_format = config.get('checkpoint_format', 'torch')          # 'tf': tf.train.Saver files (tf_checkpoint.py)
         # HIP-graph replay of the step after 2 eager steps: True (default) | False | 'auto'.  'auto' builds the graphs, then
         # times AUTO_STEPS steps replayed and AUTO_STEPS steps launched eagerly (real training steps, synchronised only
         # while calibrating) and keeps the faster mode: replay wins when the host cannot issue ~220 launches per step as
@@ -319,15 +319,7 @@ class SSD300(EvaluateMixin, F32Warmup):
                 add(ln + '.beta', (c.cout,))
                 self.sinfo[ln + '.mmean'] = (soff, (c.cout,)); soff += ops.pad_to(c.cout, 64)
                 self.sinfo[ln + '.mvar'] = (soff, (c.cout,)); soff += ops.pad_to(c.cout, 64)
-        self.nparam = off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.Mom = torch.zeros(off, device=dev)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.S = torch.zeros(soff, device=dev)
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
+        self._alloc_flat(off, soff)
         # synthetic initialisation (no checkpoint available offline): He-normal conv, zero bias,
         # BN gamma 1 / beta 0 / moving (0, 1), L2-norm scale 20 (reference SSD300.py:77)
         g = torch.Generator().manual_seed(seed)
@@ -343,48 +335,8 @@ class SSD300(EvaluateMixin, F32Warmup):
                 self.stat(ln + '.mvar').fill_(1.0)
         self._refresh_operand_copies()
 
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def stat(self, name):
-        off, shape = self.sinfo[name]
-        return self.S[off: off + int(np.prod(shape))].view(shape)
-
-    def set_param(self, name, value):
-        """value: logical shape (conv weights [K,R,S,Cin] un-padded)."""
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self.convs[name[:-2]].cin].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        """Load a dict name -> tensor in the oracle's naming ([K,R,S,Cin] weights)."""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
-        for k, v in p.items():
-            if k in self.pinfo:
-                self.set_param(k, v)
-            elif k in self.sinfo:
-                self.stat(k).copy_(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        self._sync_from_twin()                                     # mid-warm-up: the live weights are the twin's
-        out = OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-        for k in self.sinfo:
-            out[k] = self.stat(k).detach().cpu().clone()
-        return out
+    def _logical_cin(self, layer):
+        return self.convs[layer].cin
 
     def _load_pretraining_weight(self):
         """The reference initialises the 13 VGG convs from slim's vgg_16.ckpt (SSD300.py:31,193-299).
@@ -538,10 +490,6 @@ class SSD300(EvaluateMixin, F32Warmup):
         self.d_cand = torch.zeros(A, nc, dtype=torch.uint8, device=dev)
         self.refresh_wt()
 
-    def _wslice(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
     def _refresh_operand_copies(self):
         if self.DT == BF16:
             ops.cast_from_f32(self.P, self.Pc)
@@ -561,7 +509,7 @@ class SSD300(EvaluateMixin, F32Warmup):
                 c = self.convs[name]
                 d = self.desc[name]
                 kp = ops.pad_to(c.cout, 8) if name.startswith('pred') else c.cout
-                entries.append((self._wslice(name + '.w', self.P), wt, c.cout, c.k, c.k, d.C, kp))
+                entries.append((self._flat(name + '.w', self.P), wt, c.cout, c.k, c.k, d.C, kp))
             self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, self.dev)
         self._fp_batch.run()
 
@@ -603,7 +551,7 @@ class SSD300(EvaluateMixin, F32Warmup):
         return ev
 
     def _conv_fwd(self, name, src, dst, bias, relu):
-        ops.conv2d_fwd(self.desc[name], src.t, self._wslice(name + '.w', self.Pc), bias, dst.t, relu)
+        ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), bias, dst.t, relu)
 
     # ---- train_one_epoch: the NEXT batch's pixels cross PCIe under the running step (round 6) ----------------------------------------------------------
     # The f32 pixels of a batch (34.6 MB at batch 32: 0.64 ms at PCIe rate, 8 % of a step) are read exactly once, by the preprocess launch that opens the step.
@@ -642,11 +590,11 @@ class SSD300(EvaluateMixin, F32Warmup):
                     # conv + bias + ReLU + the 2x2 pool behind it in one launch; the un-pooled map is not stored (nothing else reads it: the
                     # backward pass routes by the recorded arg-max and masks by the sign of the pooled value)
                     pname = self.fused_pool[name]
-                    ops.conv2d_fwd_pool2x2(self.desc[name], a[prev].t, self._wslice(name + '.w', self.Pc), self.param(name + '.b'),
+                    ops.conv2d_fwd_pool2x2(self.desc[name], a[prev].t, self._flat(name + '.w', self.Pc), self.param(name + '.b'),
                                            a[name].t if self.keep_unpooled else None, True, a[pname].t, self.pool_idx[pname])
                     continue
                 if training and name in self.relu_bits:
-                    ops.conv2d_fwd_bits(self.desc[name], a[prev].t, self._wslice(name + '.w', self.Pc), self.param(name + '.b'), a[name].t, True,
+                    ops.conv2d_fwd_bits(self.desc[name], a[prev].t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), a[name].t, True,
                                         self.relu_bits[name])
                     continue
                 self._conv_fwd(name, a[prev], a[name], self.param(name + '.b'), True)
@@ -747,7 +695,7 @@ class SSD300(EvaluateMixin, F32Warmup):
 
     # ------------------------------------------------------------------ backward
     def _grad(self, name):
-        return self._wslice(name, self.G)
+        return self._flat(name, self.G)
 
     def _conv_bwd_params(self, name, x, dy_t, lddy):
         """Filter gradient (+ fused bias gradient).  A bias that feeds BatchNorm has an exactly
@@ -1288,58 +1236,12 @@ class SSD300(EvaluateMixin, F32Warmup):
                 slot = [k for k in names if k.endswith(tfname + '/Momentum')]
                 if slot:
                     mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                    dst = self.param(ours, self.Mom)
-                    if ours.endswith('.w'):
-                        dst.zero_()
-                        dst[..., : mv.shape[2]] = mv.permute(3, 0, 1, 2).to(self.dev)
-                    else:
-                        dst.copy_(mv.to(self.dev).view(dst.shape))
+                    self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
             else:
                 self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
         if reader.has_tensor('global_step'):
             self.global_step = int(reader.get_tensor('global_step'))
         self._refresh_operand_copies()
-
-    def _save_weight_engine(self, mode, path):
-        """SSD300.py:490-500.  config['checkpoint_format'] = 'tf' writes the reference's own files
-        (`<path>-<step>.index` + `.data-00000-of-00001` + `checkpoint`, readable by its `load_weight`); the default
-        'torch' keeps one torch file `<path>-<step>`."""
-        assert (mode in ['latest', 'best'])
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        if self.checkpoint_format == 'tf':
-            from . import tf_checkpoint
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        blob = {'params': self.export_params(), 'momentum': self.Mom.detach().cpu(),
-                'global_step': self.global_step, 'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        unknown = sorted(k for k in blob['params'] if k not in self.pinfo and k not in getattr(self, 'sinfo', {}))
-        if unknown:
-            raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
-                             'it was written by a different layer layout')
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
 
     # ------------------------------------------------------------------ data parallel
     def attach_data_parallel(self, group=None, bucket_mb=25, sync_bn=False, grad_dtype='f32', force_collectives=False, collective='torch'):

@@ -13,12 +13,12 @@ The gate: tests/test_gpu_bf16_gate.py trains each class 300 steps in f32 and req
 keeps the f32 engine."""
 import torch
 
+from .base import store_padded
+
 F32_WARMUP_DEFAULT = 300
 
 
 class F32Warmup:
-    OPT_BUFFERS = ('Mom',)            # flat optimizer-state buffers laid out like P (CenterNet: ('M1', 'M2'))
-
     def _warmup_setup(self, config, data_provider, explicit_dtype):
         from ._lib import BF16
         self._twin = None
@@ -51,12 +51,7 @@ class F32Warmup:
             for name in (None,) + tuple(src.OPT_BUFFERS):
                 v = src.param(k, None if name is None else getattr(src, name))
                 d = dst.param(k, None if name is None else getattr(dst, name))
-                if k.endswith('.w'):
-                    c = min(v.shape[-1], d.shape[-1])
-                    d.zero_()
-                    d[..., :c].copy_(v[..., :c])
-                else:
-                    d.copy_(v.view(d.shape))
+                store_padded(k, d, v[..., : d.shape[-1]])          # (a filter: the channels both paddings hold)
         if hasattr(src, 'S') and isinstance(src.S, torch.Tensor):
             dst.S.copy_(src.S.to(dst.dev))
         dst.global_step = src.global_step

@@ -24,14 +24,14 @@ from __future__ import annotations
 
 import math
 import os
-import sys
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
+from .base import DetectorBase, _Act
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
@@ -42,40 +42,17 @@ STRIDE = (8., 16., 32.)                                                     # :3
 LEAKY = 2                                                                   # odtk_bn_fwd activation code
 
 
-class _Act:
-    """rows x pitch activation; `gid` names the gradient buffer it shares with its residual partners"""
-
-    def __init__(self, name, N, H, W, C, ld, dtype, dev):
-        self.name, self.N, self.H, self.W, self.C, self.ld = name, N, H, W, C, ld
-        self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev)
-        self.gid = name
-
-
-class YOLOv3(EvaluateMixin, F32Warmup):
+class YOLOv3(EvaluateMixin, F32Warmup, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider, native_test_batch=True, num_val_optional=True)      # (this class reads num_val only with a val_generator)
         self.data_shape = config['data_shape']
-        self.num_classes = config['num_classes']
-        self.weight_decay = config['weight_decay']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else self._test_batch_size(config)
         self.scales = (config['coord_scale'], config['noobj_scale'], config['obj_scale'], config['class_scale'])
         self.num_priors = config['num_priors']
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
         priors = config['priors']
         # head l (1 = coarsest) is paired with priors[l-1] / stride[l-1], the reference's own pairing (:111-113 with :37-42)
         self.priors_flat = [float(v) / STRIDE[i] for i in range(3) for hw in priors[i] for v in hw]
         self.final_units = (self.num_classes + 5) * self.num_priors
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
         # 'f32x3' (round 5): f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
         # Round 6: the class went through the bf16 admission gate of the other classes, deterministically (tests/test_gpu_bf16_gate.py;
         # profiles/r06_bf16_gate_table.md): filter-gradient cosine of the bf16 engine against the f32 engine on 16 held-out images, minimum over the layers / median of
@@ -84,31 +61,12 @@ class YOLOv3(EvaluateMixin, F32Warmup):
         # = above the bar at 300 AND at 600 steps) the bf16 engine is NOT the default for training: with no engine named a training instance on the GPU runs
         # 'f32x3' (f32 tensors, three bf16 MFMA products per f32 product); 'bf16' -- 2.4x the step rate -- is an explicit choice (`compute_dtype='bf16'`,
         # optionally with `f32_warmup_steps`), and what bench.py's yolov3_bf16 line is quoted on.  Test mode and the CPU stand-in keep their engines.
-        engine = config.get('compute_dtype', 'f32x3' if (self.dev.type == 'cuda' and self.mode == 'train') else 'bf16')
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
+        self._set_engine(config.get('compute_dtype', 'f32x3' if (self.dev.type == 'cuda' and self.mode == 'train') else 'bf16'))
         h, w, c = self.data_shape
         assert c == 3 and h % 32 == 0 and w % 32 == 0, "YOLOv3 needs an input that is a multiple of 32 (five stride-2 stages)"
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.num_val = data_provider['num_val']
-                self.val_generator = data_provider['val_generator']
-        self.global_step = 0
         self.use_graph = bool(config.get('use_graph', True))
         self._graph, self._graph_gt, self._eager_steps = None, None, 0
-        self.dist = None
         self.sync_bn = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
-            torch.cuda.set_device(self.dev)
         self.specs = layer_specs(self.num_classes, self.num_priors)
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
@@ -132,74 +90,13 @@ class YOLOv3(EvaluateMixin, F32Warmup):
 
     def _init_parameters(self, seed):
         self.pinfo, off, self.sinfo, soff = self.param_layout(self.specs, self.chunk)
-        self.nparam = off
-        dev = self.dev
-        self.P = torch.zeros(off, device=dev)
-        self.Mom = torch.zeros(off, device=dev)
-        self.G = torch.zeros(off, device=dev)
-        self.Pc = torch.zeros(off, dtype=self.tdt, device=dev) if self.DT == BF16 else self.P
-        self.S = torch.zeros(soff, device=dev)
-        self.l2_partial = torch.zeros(ops.sgd_blocks(off), device=dev)
-        self.l2_sum = torch.zeros(1, device=dev)
+        self._alloc_flat(off, soff)
         # synthetic initialisation: variance-scaling kernels (:501), zero bias, BN gamma 1 / beta 0 / moving (0, 1)
         g = torch.Generator().manual_seed(seed)
         for name, cin, cout, k, _, _ in self.specs:
             self.set_param(name + '.w', torch.randn(cout, k, k, cin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
             self.param(name + '.gamma').fill_(1.0)
             self.stat(name + '.mvar').fill_(1.0)
-
-    def param(self, name, buf=None):
-        off, shape = self.pinfo[name]
-        buf = self.P if buf is None else buf
-        return buf[off: off + int(np.prod(shape))].view(shape)
-
-    def stat(self, name):
-        off, shape = self.sinfo[name]
-        return self.S[off: off + int(np.prod(shape))].view(shape)
-
-    def _flat(self, name, buf):
-        off, shape = self.pinfo[name]
-        return buf[off: off + int(np.prod(shape))]
-
-    def set_param(self, name, value):
-        """value in the logical shape (conv kernels [K,R,S,Cin] un-padded)"""
-        dst = self.param(name)
-        value = torch.as_tensor(value, dtype=torch.float32)
-        if name.endswith('.w'):
-            dst.zero_()
-            dst[..., : value.shape[-1]] = value.to(self.dev)
-        else:
-            dst.copy_(value.to(self.dev).view(dst.shape))
-
-    def get_param(self, name, buf=None):
-        v = self.param(name, buf).detach().cpu().clone()
-        if name.endswith('.w'):
-            v = v[..., : self._cin[name[:-2]]].contiguous()
-        return v
-
-    def load_oracle_params(self, p):
-        """dict name -> tensor in the oracle's naming ([K,R,S,Cin] kernels)"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
-        for k, v in p.items():
-            if k in self.pinfo:
-                self.set_param(k, v)
-            elif k in self.sinfo:
-                self.stat(k).copy_(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-        self._refresh_operand_copies()
-
-    def export_params(self):
-        self._sync_from_twin()                                     # mid-warm-up: the live weights are the twin's
-        out = OrderedDict((k, self.get_param(k)) for k in self.pinfo)
-        for k in self.sinfo:
-            out[k] = self.stat(k).detach().cpu().clone()
-        return out
-
-    def _refresh_operand_copies(self):
-        if self.DT == BF16:
-            ops.cast_from_f32(self.P, self.Pc)
-        if getattr(self, '_fp_batch', None) is not None:
-            self._fp_batch.run()
 
     # ------------------------------------------------------------------ the graph: buffers + launch plan
     def _build(self):
@@ -365,17 +262,6 @@ class YOLOv3(EvaluateMixin, F32Warmup):
                 ops.upsample2x_bwd(dcat[:, bottom.C:], y.ld, self.grad_of(lat), lat.ld, lat.N, lat.H, lat.W, lat.C, False)
 
     # ------------------------------------------------------------------ public: training
-    def _set_batch_engine(self, images, ground_truth):
-        images = torch.as_tensor(images, dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images, non_blocking=True)
-        gt = torch.as_tensor(ground_truth, dtype=torch.float32)
-        if self.gt is None or self.gt.shape != gt.shape:
-            self.gt = torch.zeros(gt.shape, device=self.dev)
-        self.gt.copy_(gt, non_blocking=True)
-
     def _step_body(self):
         self.G.zero_()
         self._forward(True)
@@ -408,28 +294,6 @@ class YOLOv3(EvaluateMixin, F32Warmup):
         self._fp_batch.run()
         self.global_step += 1
         return 0.5 * self.loss_parts[:, 4].mean() + self.weight_decay * self.l2_sum        # YOLOv3.py:311-315 (pre-update weights)
-
-    def train_one_epoch(self, lr):
-        if callable(self.train_initializer):
-            self.train_initializer()
-        mean_loss = []
-        num_iters = self.num_train // self.batch_size
-        it = iter(self.train_iterator)
-        for i in range(num_iters):
-            try:
-                images, gt = next(it)
-            except StopIteration:
-                it = iter(self.train_iterator)
-                images, gt = next(it)
-            self.set_batch(images, gt)
-            loss = float(self.train_step(lr).item())
-            if self.verbose:
-                sys.stdout.write('\r>> ' + 'iters ' + str(i) + str('/') + str(num_iters) + ' loss ' + str(loss))
-                sys.stdout.flush()
-            mean_loss.append(loss)
-        if self.verbose:
-            sys.stdout.write('\n')
-        return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
     NATIVE_TEST_IMAGES = True
@@ -469,11 +333,6 @@ class YOLOv3(EvaluateMixin, F32Warmup):
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def _logical(self, name, buf):
-        """parameter `name` out of a flat buffer (P or Mom) in TensorFlow's layout: kernels HWIO, un-padded"""
-        v = self.get_param(name, buf)
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
-
     def export_tf_variables(self):
         """what the reference's `tf.train.Saver()` (YOLOv3.py:377-381) writes: every variable of its graph under its name
         (reference_variable_map), global_step, and the momentum slots `<variable>/Momentum` (the optimizer is created outside any
@@ -507,53 +366,10 @@ class YOLOv3(EvaluateMixin, F32Warmup):
             self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
             if not backbone_trainables_only and tfname + '/Momentum' in names:
                 mv = torch.from_numpy(reader.get_tensor(tfname + '/Momentum'))
-                dst = self.param(ours, self.Mom)
-                if ours.endswith('.w'):
-                    dst.zero_()
-                    dst[..., : mv.shape[2]] = mv.permute(3, 0, 1, 2).to(self.dev)
-                else:
-                    dst.copy_(mv.to(self.dev).view(dst.shape))
+                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
         if not backbone_trainables_only and reader.has_tensor('global_step'):
             self.global_step = int(reader.get_tensor('global_step'))
         self._refresh_operand_copies()
-
-    def _save_weight_engine(self, mode, path):
-        """YOLOv3.py:466-475.  config['checkpoint_format'] = 'tf' writes tf.train.Saver files (tf_checkpoint.py)."""
-        assert (mode in ['latest', 'best'])
-        dirname = os.path.dirname(path)
-        if dirname and not os.path.exists(dirname):
-            os.makedirs(dirname)
-            print(dirname, 'does not exist, create it done')
-        if self.config.get('checkpoint_format', 'torch') == 'tf':
-            from . import tf_checkpoint
-            prefix = path + '-' + str(self.global_step)
-            tf_checkpoint.write_bundle(prefix, self.export_tf_variables())
-            tf_checkpoint.update_checkpoint_state(prefix)
-            print('save', mode, 'model in', path, 'successfully')
-            return
-        blob = {'params': self.export_params(), 'momentum': self.Mom.detach().cpu(), 'global_step': self.global_step, 'layout': {k: (int(o), tuple(int(x) for x in shp)) for k, (o, shp) in self.pinfo.items()}}
-        torch.save(blob, path + '-' + str(self.global_step))
-        print('save', mode, 'model in', path, 'successfully')
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        unknown = sorted(k for k in blob['params'] if k not in self.pinfo and k not in getattr(self, 'sinfo', {}))
-        if unknown:
-            raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
-                             'it was written by a different layer layout')
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
 
     def load_pretraining_weight(self, path):
         """YOLOv3.py:480-482 restores the trainable 'backone' variables: here the c0 .. c51 entries of a saved file"""
