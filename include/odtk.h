@@ -407,6 +407,21 @@ int odtk_ssd_decode_batched(const float* pred, int N, int A, int C, int ld, cons
 int odtk_retina_decode_batched(const float* pconf, const float* pbox, int N, int A, int C, const float* yx, const float* hw, float score_thr,
                                float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
 
+/* RefineDet / PFPNetR decode of N images in one launch: odtk_refinedet_decode per image (the same kernel, one y-block per image), bit for bit; anchors shared.
+ * arm_loc, odm_loc [N][A][4], arm_conf [N][A][2], odm_conf [N][A][C] -> conf, cand [N][A][C-1], boxes [N][A][4], keep [N][A].  1 <= N <= 65535. */
+int odtk_refinedet_decode_batched(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, int N, int A, int C,
+                                  const float* yx, const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand,
+                                  void* stream);
+
+/* CenterNet decode of N images: keypoints [N][H][W][C] logits, offset / size [N][H][W][2] -> scores [N][top_k], bbox [N][top_k][4] y1,x1,y2,x2 px, class_id
+ * [N][top_k], counts [N]; rows behind an image's count are not written.  The sigmoid / arg-max kernel runs over the N*H*W pixels in one launch; the 3x3 peak
+ * test, the threshold and the bitonic top-k run with one workgroup per image (grid N, up to 128 KiB of LDS keys each).  Per image the outputs are what
+ * odtk_centernet_decode gives on that image alone, bit for bit (descending score, the lower pixel index first on equal scores).  H*W <= 16384,
+ * 1 <= N <= 65535.  workspace: odtk_centernet_decode_workspace_bytes(N, H, W) bytes (N score planes + N class planes). */
+long long odtk_centernet_decode_workspace_bytes(int N, int H, int W);
+int odtk_centernet_decode_batched(const float* keypoints, const float* offset, const float* size, int N, int H, int W, int C, float stride,
+                                  float score_threshold, int top_k, float* scores, float* bbox, int* class_id, int* counts, void* workspace, void* stream);
+
 /* Greedy NMS for N * num_classes problems in one launch chain.  Problem (img, c): boxes at boxes + img*box_istride (floats) [n][4]; score i at
  * scores[img*score_istride + c*score_cstride + i*score_estride]; valid[img*valid_istride + c*valid_cstride + i*valid_estride] (u8, NULL = all valid) must
  * equal `valid_value`; n_dev (device ints [N], or NULL) limits image img to its first min(n, n_dev[img]) boxes.  Picks in order go to

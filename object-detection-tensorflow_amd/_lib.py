@@ -142,6 +142,9 @@ SIGNATURES = {
     "odtk_augment_images": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "odtk_ssd_decode_batched": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "odtk_retina_decode_batched": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_refinedet_decode_batched": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_centernet_decode_workspace_bytes": (_ll, [_i, _i, _i]),
+    "odtk_centernet_decode_batched": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_nms_image_class": (_i, [_vp, _ll, _vp, _ll, _ll, _i, _vp, _ll, _ll, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp]),
     "odtk_compact_rows": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "odtk_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

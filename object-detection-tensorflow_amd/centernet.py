@@ -90,7 +90,7 @@ class CenterNet(EvaluateMixin, F32Warmup, DetectorBase):
     PROGRESS_FROM = 1                                          # CenterNet.py's epoch loop prints i + 1
 
     def __init__(self, config, data_provider):
-        self._prologue(config, data_provider, nms=False)
+        self._prologue(config, data_provider, native_test_batch=True, nms=False)
         self.input_size = config['input_size']
         self.data_shape = [self.input_size, self.input_size, 3] if config['data_format'] == 'channels_last' else [3, self.input_size, self.input_size]
         self.prob = 1. - config['keep_prob']                   # unused, as in the reference
@@ -397,7 +397,22 @@ class CenterNet(EvaluateMixin, F32Warmup, DetectorBase):
         return self.loss_parts[:, 3].mean() + self.weight_decay * self.l2_sum          # CenterNet.py:152-153 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
+    NATIVE_TEST_IMAGES = True
+    _tail_batched = None
+
+    def test_images(self, images):
+        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then odtk_centernet_decode_batched (one workgroup per image for the peak
+        test + top-k) and one read-back (heads.CenterNetBatched).  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
+        n = self._stage_test_images(images)
+        self._forward(False, normalize=bool(self.config.get('test_normalize', False)))       # the reference's quirk, as in test_one_image
+        t = self._tail_batched
+        if t is None:
+            t = self._tail_batched = heads.CenterNetBatched(self.batch_size, self.kp_act.H, self.kp_act.W, self.top_k_results_output, self.dev)
+        return t(self.keypoints, self.offset, self.size, self.score_threshold, STRIDE, n)
+
     def test_one_image(self, images):
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self.test_images(images)[0]
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)

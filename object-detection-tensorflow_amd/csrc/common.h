@@ -75,4 +75,13 @@ int nms_image_class_launch(const float* boxes, long long box_istride, const floa
 int decode_launch(const float* pred, long long pred_istride, int N, int A, int C, int ld, const float* box, long long box_istride, int ldb, const float* yx,
                   const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
 
+// dense_heads.hip / refinedet.hip: the single-image decodes with an image index (N images per launch; image i's operands px_istride pixels / row_istride rows
+// behind those of image i - 1, 0 with N = 1; outputs and the CenterNet workspace packed per image) -- behind odtk_centernet_decode / odtk_refinedet_decode
+// and their batched forms (csrc/detect_batched.hip).  The callers check the pointers and N, the launchers the shapes.
+int centernet_decode_launch(const float* keypoints, const float* offset, const float* size, long long px_istride, int N, int H, int W, int C, float stride,
+                            float score_threshold, int top_k, float* scores, float* bbox, int* class_id, int* count, void* workspace, void* stream);
+int refinedet_decode_launch(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, long long row_istride, int N, int A,
+                            int C, const float* yx, const float* hw, float score_threshold, float* conf, float* boxes, unsigned char* keep,
+                            unsigned char* cand, void* stream);
+
 }  // namespace odtk

@@ -185,11 +185,14 @@ __global__ void __launch_bounds__(DH_THREADS) centernet_final_kernel(const CnArg
     }
 }
 
-// ---- decode (CenterNet.py:159-185), one image
-__global__ void __launch_bounds__(DH_THREADS) centernet_score_kernel(const float* __restrict__ keypoints, int HW, int C,
+// ---- decode (CenterNet.py:159-185): blockIdx.y = image; keypoints of image i start px_istride pixels behind those of image i - 1, score / cls are [N][HW]
+__global__ void __launch_bounds__(DH_THREADS) centernet_score_kernel(const float* __restrict__ keypoints, long long px_istride, int HW, int C,
                                                                      float* __restrict__ score, int* __restrict__ cls) {
     const int p = blockIdx.x * DH_THREADS + threadIdx.x;
     if (p >= HW) return;
+    const size_t img = blockIdx.y;
+    keypoints += img * (size_t)px_istride * C;
+    score += img * HW; cls += img * HW;
     float best = sigmoidf_(keypoints[(size_t)p * C]);
     int bc = 0;
     for (int c = 1; c < C; ++c) {
@@ -199,15 +202,20 @@ __global__ void __launch_bounds__(DH_THREADS) centernet_score_kernel(const float
     score[p] = best; cls[p] = bc;
 }
 
-// 3x3 peak test, threshold, top-k (descending score, lower index first): one workgroup, bitonic sort in LDS
+// 3x3 peak test, threshold, top-k (descending score, lower index first): one workgroup PER IMAGE (blockIdx.x) with its own counter and key array,
+// bitonic sort in LDS; offset / size of image i px_istride pixels behind those of image i - 1, the outputs [N][top_k | top_k * 4 | top_k], out_count [N]
 __global__ void __launch_bounds__(1024) centernet_topk_kernel(const float* __restrict__ score, const int* __restrict__ cls,
-                                                              const float* __restrict__ offset, const float* __restrict__ size,
+                                                              const float* __restrict__ offset, const float* __restrict__ size, long long px_istride,
                                                               int H, int W, float stride, float thr, int top_k,
                                                               float* __restrict__ out_scores, float* __restrict__ out_bbox,
                                                               int* __restrict__ out_cls, int* __restrict__ out_count) {
     extern __shared__ unsigned long long keys[];
     __shared__ int cnt;
     const int HW = H * W;
+    const size_t img = blockIdx.x;
+    score += img * HW; cls += img * HW;
+    offset += img * (size_t)px_istride * 2; size += img * (size_t)px_istride * 2;
+    out_scores += img * top_k; out_bbox += img * (size_t)top_k * 4; out_cls += img * top_k; out_count += img;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
     for (int p = threadIdx.x; p < HW; p += 1024) {
@@ -659,23 +667,30 @@ extern "C" int odtk_centernet_loss(const float* keypoints, const float* offset, 
     return ODTK_OK;
 }
 
-extern "C" int odtk_centernet_decode(const float* keypoints, const float* offset, const float* size, int H, int W, int C,
-                                     float stride, float score_threshold, int top_k, float* scores, float* bbox, int* class_id,
-                                     int* count, void* workspace, void* stream) {
-    ODTK_REQUIRE(keypoints && offset && size && scores && bbox && class_id && count && workspace, "centernet_decode: null pointer");
+// the decode launches of N images (csrc/detect_batched.hip: odtk_centernet_decode_batched); workspace = N score planes + N class planes
+int odtk::centernet_decode_launch(const float* keypoints, const float* offset, const float* size, long long px_istride, int N, int H, int W, int C,
+                                  float stride, float score_threshold, int top_k, float* scores, float* bbox, int* class_id, int* count, void* workspace,
+                                  void* stream) {
     ODTK_REQUIRE(H > 0 && W > 0 && C > 0 && top_k > 0 && H * W <= 16384, "centernet_decode: H=%d W=%d (H*W <= 16384) C=%d top_k=%d", H, W, C, top_k);
     ODTK_REQUIRE(score_threshold >= 0.f, "centernet_decode: score_threshold must be >= 0");
     hipStream_t st = (hipStream_t)stream;
     float* score = (float*)workspace;
-    int* cls = (int*)(score + (size_t)H * W);
-    hipLaunchKernelGGL(centernet_score_kernel, dim3(ceil_div(H * W, DH_THREADS)), dim3(DH_THREADS), 0, st, keypoints, H * W, C, score, cls);
+    int* cls = (int*)(score + (size_t)N * H * W);
+    hipLaunchKernelGGL(centernet_score_kernel, dim3(ceil_div(H * W, DH_THREADS), N), dim3(DH_THREADS), 0, st, keypoints, px_istride, H * W, C, score, cls);
     int n2 = 1;
     while (n2 < H * W) n2 <<= 1;
     ODTK_CHECK_HIP(hipFuncSetAttribute((const void*)centernet_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8));
-    hipLaunchKernelGGL(centernet_topk_kernel, dim3(1), dim3(1024), (size_t)n2 * 8, st, score, cls, offset, size, H, W, stride,
+    hipLaunchKernelGGL(centernet_topk_kernel, dim3(N), dim3(1024), (size_t)n2 * 8, st, score, cls, offset, size, px_istride, H, W, stride,
                        score_threshold, top_k, scores, bbox, class_id, count);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
+}
+
+extern "C" int odtk_centernet_decode(const float* keypoints, const float* offset, const float* size, int H, int W, int C,
+                                     float stride, float score_threshold, int top_k, float* scores, float* bbox, int* class_id,
+                                     int* count, void* workspace, void* stream) {
+    ODTK_REQUIRE(keypoints && offset && size && scores && bbox && class_id && count && workspace, "centernet_decode: null pointer");
+    return centernet_decode_launch(keypoints, offset, size, 0, 1, H, W, C, stride, score_threshold, top_k, scores, bbox, class_id, count, workspace, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- FCOS

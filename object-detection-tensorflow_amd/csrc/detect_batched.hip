@@ -2,6 +2,8 @@
 // than the NMS takes per problem, and the detection pack (per-image counts -> exclusive scan -> scores / bbox / class_id in the reference's concat order).
 // The decode and NMS launches are the kernels of boxes.hip (decode_launch / nms_image_class_launch): per image they compute what odtk_ssd_decode /
 // odtk_retina_decode / odtk_nms_batched compute on that image alone, bit for bit.  No float atomics anywhere: two runs give identical bytes.
+// CenterNet (peak test + top-k, no NMS) and RefineDet / PFPNetR (two-stage decode, then the tail above) come in the same way: centernet_decode_launch of
+// dense_heads.hip and refinedet_decode_launch of refinedet.hip with N images.
 #include "common.h"
 
 namespace odtk {
@@ -136,6 +138,26 @@ extern "C" int odtk_retina_decode_batched(const float* pconf, const float* pbox,
     ODTK_REQUIRE(C > 1 && C <= 32 && A > 0, "retina_decode_batched: C=%d A=%d unsupported", C, A);
     ODTK_REQUIRE(N > 0 && N <= 65535, "retina_decode_batched: N=%d out of range", N);
     return decode_launch(pconf, (long long)A * C, N, A, C, C, pbox, (long long)A * 4, 4, yx, hw, score_thr, conf, boxes, keep, cand, stream);
+}
+
+extern "C" int odtk_refinedet_decode_batched(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, int N, int A, int C,
+                                             const float* yx, const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep,
+                                             unsigned char* cand, void* stream) {
+    ODTK_REQUIRE(arm_loc && arm_conf && odm_loc && odm_conf && yx && hw && conf && boxes && keep && cand, "refinedet_decode_batched: null pointer");
+    ODTK_REQUIRE(N > 0 && N <= 65535, "refinedet_decode_batched: N=%d out of range (1..65535)", N);
+    return refinedet_decode_launch(arm_loc, arm_conf, odm_loc, odm_conf, A, N, A, C, yx, hw, score_thr, conf, boxes, keep, cand, stream);
+}
+
+// N score planes (f32) + N class planes (i32); odtk_centernet_workspace_bytes (the loss's sizing) holds ONE of each
+extern "C" long long odtk_centernet_decode_workspace_bytes(int N, int H, int W) { return (long long)N * H * W * 8; }
+
+extern "C" int odtk_centernet_decode_batched(const float* keypoints, const float* offset, const float* size, int N, int H, int W, int C, float stride,
+                                             float score_threshold, int top_k, float* scores, float* bbox, int* class_id, int* counts, void* workspace,
+                                             void* stream) {
+    ODTK_REQUIRE(keypoints && offset && size && scores && bbox && class_id && counts && workspace, "centernet_decode_batched: null pointer");
+    ODTK_REQUIRE(N > 0 && N <= 65535, "centernet_decode_batched: N=%d out of range (1..65535)", N);
+    return centernet_decode_launch(keypoints, offset, size, (long long)H * W, N, H, W, C, stride, score_threshold, top_k, scores, bbox, class_id, counts,
+                                   workspace, stream);
 }
 
 extern "C" int odtk_nms_image_class(const float* boxes, long long box_istride, const float* scores, long long score_istride, long long score_cstride,

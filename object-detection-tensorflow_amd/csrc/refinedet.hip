@@ -141,13 +141,17 @@ __global__ void __launch_bounds__(64) refinedet_loss_final_kernel(const RdArgs k
     o[7] = t[6];
 }
 
-// RefineDet.py:189-206: one thread per anchor
+// RefineDet.py:189-206: one thread per anchor, blockIdx.y = image: its four prediction tensors start row_istride rows behind those of the image before,
+// the outputs are [N][A][..]; the anchors are shared
 __global__ void refinedet_decode_kernel(const float* __restrict__ arm_loc, const float* __restrict__ arm_conf, const float* __restrict__ odm_loc,
-                                        const float* __restrict__ odm_conf, int A, int C, const float* __restrict__ yx, const float* __restrict__ hw,
-                                        float thr, float* __restrict__ conf, float* __restrict__ boxes, unsigned char* __restrict__ keep,
-                                        unsigned char* __restrict__ cand) {
+                                        const float* __restrict__ odm_conf, long long row_istride, int A, int C, const float* __restrict__ yx,
+                                        const float* __restrict__ hw, float thr, float* __restrict__ conf, float* __restrict__ boxes,
+                                        unsigned char* __restrict__ keep, unsigned char* __restrict__ cand) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= A) return;
+    const size_t img = blockIdx.y, in0 = img * (size_t)row_istride, out0 = img * (size_t)A;
+    arm_loc += in0 * 4; arm_conf += in0 * 2; odm_loc += in0 * 4; odm_conf += in0 * C;
+    conf += out0 * (C - 1); boxes += out0 * 4; keep += out0; cand += out0 * (C - 1);
     const float z0 = arm_conf[2 * a], z1 = arm_conf[2 * a + 1];
     const float am = fmaxf(z0, z1);
     const float e0 = expf(z0 - am), e1 = expf(z1 - am);
@@ -222,13 +226,20 @@ extern "C" int odtk_refinedet_loss(const float* arm_loc, const float* arm_conf, 
     return ODTK_OK;
 }
 
+// the decode launch of N images (csrc/detect_batched.hip: odtk_refinedet_decode_batched)
+int odtk::refinedet_decode_launch(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, long long row_istride, int N,
+                                  int A, int C, const float* yx, const float* hw, float score_threshold, float* conf, float* boxes, unsigned char* keep,
+                                  unsigned char* cand, void* stream) {
+    ODTK_REQUIRE(A > 0 && C > 1 && C <= RD_MAXC, "refinedet_decode: A=%d C=%d out of range", A, C);
+    hipLaunchKernelGGL(refinedet_decode_kernel, dim3((A + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, arm_loc, arm_conf, odm_loc, odm_conf,
+                       row_istride, A, C, yx, hw, score_threshold, conf, boxes, keep, cand);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+
 extern "C" int odtk_refinedet_decode(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, int A, int C,
                                      const float* yx, const float* hw, float score_threshold, float* conf, float* boxes, unsigned char* keep,
                                      unsigned char* cand, void* stream) {
     ODTK_REQUIRE(arm_loc && arm_conf && odm_loc && odm_conf && yx && hw && conf && boxes && keep && cand, "refinedet_decode: null pointer");
-    ODTK_REQUIRE(A > 0 && C > 1 && C <= RD_MAXC, "refinedet_decode: A=%d C=%d out of range", A, C);
-    hipLaunchKernelGGL(refinedet_decode_kernel, dim3((A + 255) / 256), dim3(256), 0, (hipStream_t)stream, arm_loc, arm_conf, odm_loc, odm_conf, A, C, yx,
-                       hw, score_threshold, conf, boxes, keep, cand);
-    ODTK_LAUNCH_CHECK();
-    return ODTK_OK;
+    return refinedet_decode_launch(arm_loc, arm_conf, odm_loc, odm_conf, 0, 1, A, C, yx, hw, score_threshold, conf, boxes, keep, cand, stream);
 }

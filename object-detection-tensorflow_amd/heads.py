@@ -2,8 +2,9 @@
 per-class NMS (the SSD300 NMS path) -> [scores f32[K], bbox f32[K,4] y1x1y2x2 px, class_id i32[K]], i.e. what each class
 stores in `self.detection_pred` (RetinaNet.py:224-256, YOLOv3.py:320-368, FCOS.py:197-265, CenterNet.py:159-185, RefineDet.py:189-230);
 for RefineDet also the training-side chain matching -> ARM hard-negative mining -> two-stage loss (`refinedet_loss`).
-Inputs are the head outputs of ONE image as device tensors; `BatchedTail` is the same tail for N images per launch (test_images).  Product path: no CPU
-fallback, no use of the test oracles."""
+Inputs are the head outputs of ONE image as device tensors; `BatchedTail` is the same tail for N images per launch (test_images) and `CenterNetBatched`
+CenterNet's peak test + top-k for N images.  Native test_images: SSD300, SSD512, YOLOv3, RetinaNet, CenterNet, RefineDet320, PFPNetR; FCOS, YOLOv2 and
+Light-Head R-CNN loop over test_one_image.  Product path: no CPU fallback, no use of the test oracles."""
 from __future__ import annotations
 
 import torch
@@ -114,6 +115,52 @@ class BatchedTail:
 
     def __call__(self, conf, boxes, cand, iou_thr, n_images=None):
         self.launch(conf, boxes, cand, iou_thr)
+        return self.read(n_images)
+
+
+class CenterNetBatched:
+    """CenterNet's tail for N images at once: odtk_centernet_decode_batched (sigmoid / arg-max over all pixels, then one workgroup per image for the 3x3 peak
+    test, the threshold and the top-k) -> ONE read-back per batch through a pinned host buffer.  Per image the result is what `centernet_detect` returns for
+    that image alone, bit for bit.  One buffer of 4-byte words travels back: counts [N] | scores [N, top_k] | bbox [N, top_k, 4] | class_id [N, top_k]; rows
+    behind an image's count are never read."""
+
+    def __init__(self, N, H, W, top_k, device):
+        self.N, self.H, self.W, self.K = int(N), int(H), int(W), int(top_k)
+        dev = self.dev = torch.device(device)
+        N, K = self.N, self.K
+        self.words = torch.zeros(N + 6 * N * K, dtype=torch.int32, device=dev)
+        self._o_scores, self._o_bbox, self._o_cid = N, N + N * K, N + 5 * N * K
+        self.counts = self.words[:N]
+        self.scores = self.words[self._o_scores: self._o_bbox].view(torch.float32).view(N, K)
+        self.bbox = self.words[self._o_bbox: self._o_cid].view(torch.float32).view(N, K, 4)
+        self.class_id = self.words[self._o_cid:].view(N, K)
+        self.host = torch.zeros(self.words.shape, dtype=torch.int32, pin_memory=True) if dev.type == 'cuda' else None
+        self.ws = None                                  # N score planes + N class planes, allocated with the first launch
+
+    def launch(self, keypoints, offset, size, score_thr, stride=4.0):
+        """the device side (no synchronisation): after it self.words holds the batch's detections"""
+        assert tuple(keypoints.shape[:3]) == (self.N, self.H, self.W) and tuple(offset.shape) == tuple(size.shape) == (self.N, self.H, self.W, 2)
+        if self.ws is None:
+            self.ws = ops.centernet_decode_workspace(self.N, self.H, self.W, self.dev)
+        ops.centernet_decode_batched(keypoints, offset, size, stride, score_thr, self.K, self.scores, self.bbox, self.class_id, self.counts, self.ws)
+
+    def read(self, n_images=None):
+        """the one read-back: list of [scores f32[k], bbox f32[k, 4], class_id i32[k]] (numpy) of the first n_images images, k = that image's count"""
+        n_images = self.N if n_images is None else int(n_images)
+        if self.host is not None:
+            self.host.copy_(self.words, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            h = self.host.numpy()
+        else:
+            h = self.words.numpy()
+        N, K = self.N, self.K
+        sc = h[self._o_scores: self._o_bbox].view('float32').reshape(N, K)
+        bb = h[self._o_bbox: self._o_cid].view('float32').reshape(N, K, 4)
+        ci = h[self._o_cid:].reshape(N, K)
+        return [[sc[n, :h[n]].copy(), bb[n, :h[n]].copy(), ci[n, :h[n]].copy()] for n in range(n_images)]
+
+    def __call__(self, keypoints, offset, size, score_thr, stride=4.0, n_images=None):
+        self.launch(keypoints, offset, size, score_thr, stride)
         return self.read(n_images)
 
 

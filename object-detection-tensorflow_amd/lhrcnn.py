@@ -33,6 +33,7 @@ import torch
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
 from .refinedet import RefineDet320
+from .voc_eval import EvaluateMixin
 
 ANCHOR_SCALES = [32, 64, 128, 256, 512]
 ANCHOR_RATIOS = [0.5, 1.0, 2.0]
@@ -364,6 +365,9 @@ class LHRCNN(RefineDet320):
         return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ inference
+    NATIVE_TEST_IMAGES = False              # the batched tail of refinedet.RefineDet320 is not this class's: test_images is the loop over test_one_image
+    test_images = EvaluateMixin.test_images
+
     def test_one_image(self, images):
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:

@@ -430,6 +430,26 @@ def retina_decode_batched(pconf, pbox, yx, hw, thr, conf, boxes, keep, cand):
     call("odtk_retina_decode_batched", _p(pconf), _p(pbox), N, A, Cn, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep), _p(cand), _stream())
 
 
+def refinedet_decode_batched(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr, conf, boxes, keep, cand):
+    """odtk_refinedet_decode for N images in one launch: arm_loc / odm_loc [N, A, 4], arm_conf [N, A, 2], odm_conf [N, A, C] -> conf, cand [N, A, C-1],
+    boxes [N, A, 4], keep [N, A]"""
+    N, A, Cn = odm_conf.shape
+    call("odtk_refinedet_decode_batched", _p(arm_loc), _p(arm_conf), _p(odm_loc), _p(odm_conf), N, A, Cn, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes),
+         _p(keep), _p(cand), _stream())
+
+
+def centernet_decode_workspace(N, H, W, device):
+    return torch.empty(int(_lib.load().odtk_centernet_decode_workspace_bytes(N, H, W)), dtype=torch.uint8, device=device)
+
+
+def centernet_decode_batched(keypoints, offset, size, stride, score_threshold, top_k, scores, bbox, class_id, counts, ws):
+    """odtk_centernet_decode for N images [N, H, W, C] in two launches: scores [N, top_k], bbox [N, top_k, 4], class_id [N, top_k], counts [N] (rows behind
+    an image's count are left as they are); ws: centernet_decode_workspace(N, H, W)"""
+    N, H, W, Cn = keypoints.shape
+    call("odtk_centernet_decode_batched", _p(keypoints), _p(offset), _p(size), N, H, W, Cn, float(stride), float(score_threshold), int(top_k), _p(scores),
+         _p(bbox), _p(class_id), _p(counts), _p(ws), _stream())
+
+
 def nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, score_estride, valid, valid_istride, valid_cstride, valid_estride, valid_value,
                     n, n_dev, N, num_classes, max_out, iou_thr, out_idx, cap, out_cnt):
     """greedy NMS of N * num_classes problems (image x class) in one launch chain; operand addressing as in include/odtk.h"""

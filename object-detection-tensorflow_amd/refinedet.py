@@ -92,7 +92,7 @@ class RefineDet320(EvaluateMixin, F32Warmup, DetectorBase):
         return layer_specs(num_classes)
 
     def __init__(self, config, data_provider):
-        self._prologue(config, data_provider)
+        self._prologue(config, data_provider, native_test_batch=True)
         self.input_size = config['input_size']
         self.data_shape = [self.input_size, self.input_size, 3] if config['data_format'] == 'channels_last' else [3, self.input_size, self.input_size]
         self.num_classes = config['num_classes'] + 1          # background = LAST index
@@ -588,7 +588,32 @@ class RefineDet320(EvaluateMixin, F32Warmup, DetectorBase):
         return self._data_loss + self.weight_decay * self.l2_sum      # RefineDet.py:180-184 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
+    NATIVE_TEST_IMAGES = True               # RefineDet320 and pfpnet.PFPNetR (inherited); yolov2.YOLOv2 and lhrcnn.LHRCNN reset it: their tails are not batched
+    _tail_batched = None
+
+    def test_images(self, images):
+        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_refinedet_decode_batched -> odtk_nms_image_class
+        -> odtk_detection_pack -> one read-back (heads.BatchedTail; 6 375 / 16 320 anchors at 320 / 512: below the NMS capacity, no compaction).  Returns n
+        [scores, bbox, class_id] triples as test_one_image gives them."""
+        n = self._stage_test_images(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # the reference's quirk, as in test_one_image
+        N, A, nc = self.batch_size, self.A, self.num_classes - 1
+        t = self._tail_batched
+        if t is None:
+            t = self._tail_batched = heads.BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
+            # the decode's outputs ride on the tail object, as in ssd300.py / retinanet.py / yolov3.py (BatchedTail allocates only what the NMS and the pack write;
+            # tools/inference_bench.py reads t.conf / t.boxes / t.keep / t.cand of every native class)
+            t.conf = torch.zeros(N, A, nc, device=self.dev)
+            t.boxes = torch.zeros(N, A, 4, device=self.dev)
+            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
+            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
+        ops.refinedet_decode_batched(self.arm_loc, self.arm_conf, self.odm_loc, self.odm_conf, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf,
+                                     t.boxes, t.keep, t.cand)
+        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
+
     def test_one_image(self, images):
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self.test_images(images)[0]
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)

@@ -207,9 +207,9 @@ class EvaluateMixin:
     copy per batch_size (built with test_batch_size = B) in `self._eval_models`; each copy holds its own weights and activation buffers at N = B on the
     device until the entry is deleted (`del model._eval_models[B]`), so evaluate with ONE batch size per run rather than sweeping them.
 
-    `test_images(images)` here is the form every class has: a LOOP over `test_one_image`, NOT batched (FCOS, CenterNet, YOLOv2, RefineDet, PFPNetR,
-    Light-Head R-CNN).  SSD300, SSD512, YOLOv3 and RetinaNet override it with one forward pass at N = test_batch_size and the batched tail
-    (heads.BatchedTail)."""
+    `test_images(images)` here is the fallback form: a LOOP over `test_one_image`, NOT batched (FCOS, YOLOv2, Light-Head R-CNN).  Seven classes override
+    it with one forward pass at N = test_batch_size and a batched tail: SSD300, SSD512, YOLOv3, RetinaNet, RefineDet320 and PFPNetR (heads.BatchedTail)
+    and CenterNet (heads.CenterNetBatched)."""
 
     NATIVE_TEST_IMAGES = False               # True in the classes whose test_images is one batched forward + tail
 

@@ -20,6 +20,7 @@ import torch
 from . import heads, ops
 from ._lib import BF16, F32, F32X3
 from .refinedet import RefineDet320
+from .voc_eval import EvaluateMixin
 
 BACKBONE = [(32, 3), 'P', (64, 3), 'P', (128, 3), (64, 1), (128, 3), 'P', (256, 3), (128, 1), (256, 3), 'P',
             (512, 3), (256, 1), (512, 3), (256, 1), (512, 3), 'P', (1024, 3), (512, 1), (1024, 3), (512, 1), (1024, 3)]
@@ -159,6 +160,9 @@ class YOLOv2(RefineDet320):
     def _loss_step(self):
         parts = self.loss(self.pred, self.gt, 1.0 / self.loss_divisor_batch, STRIDE)
         return parts[:, 4].sum() / self.batch_size
+
+    NATIVE_TEST_IMAGES = False              # the batched tail of refinedet.RefineDet320 is not this class's: test_images is the loop over test_one_image
+    test_images = EvaluateMixin.test_images
 
     def test_one_image(self, images):
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)

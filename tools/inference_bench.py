@@ -1,12 +1,12 @@
 """Inference and evaluation rates, per-image path against batched path, in ONE process on ONE set of weights; prints one JSON line.
 
-Per class and engine (--classes ssd300,ssd512,yolov3,retinanet; engines of the class or --engines):
+Per class and engine (--classes ssd300,ssd512,yolov3,retinanet,centernet,refinedet,pfpnet; engines of the class or --engines):
   * the loop of test_one_image (the per-image path: a model built without test_batch_size);
   * test_images at B = 1, 8, 32 (16 for RetinaNet 800 x 800) on models built with test_batch_size = B from the same weights;
   * evaluate() at batch_size 1 and at the largest B over the same validation generator, with the share of the wall time spent in Python staging
     (VOCEvaluator.add) and in result();
   * the kernel times of the batched tail at the largest B by HIP events: the decode launch, and compaction + NMS + pack (BatchedTail.launch), plus the
-    read-back (wall clock).
+    read-back (wall clock); CenterNet's tail is the decode alone (score / arg-max + one top-k workgroup per image, heads.CenterNetBatched).
 Only pairs measured in the same process count: two boxes of a pool differ by more than most changes.  Synthetic weights and pixels; the score threshold is
 lowered for the SSD family (--score-threshold, default 0.01) so that the tail has detections to carry; the other classes keep their configuration's
 threshold (at 0.01 a random-weight RetinaNet has more candidate rows than the NMS takes)."""
@@ -25,13 +25,17 @@ import odtk             # noqa: E402
 from odtk import ops    # noqa: E402
 import bench_configs as BCFG    # noqa: E402
 
-CLASSES = {'ssd300': 'SSD300', 'ssd512': 'SSD512', 'yolov3': 'YOLOv3', 'retinanet': 'RetinaNet'}
-ENGINES = {'ssd300': ['f32', 'f32x3', 'bf16'], 'ssd512': ['f32'], 'yolov3': ['f32'], 'retinanet': ['f32']}
-BATCHES = {'ssd300': [1, 8, 32], 'ssd512': [1, 8, 32], 'yolov3': [1, 8, 32], 'retinanet': [1, 8, 16]}
+CLASSES = {'ssd300': 'SSD300', 'ssd512': 'SSD512', 'yolov3': 'YOLOv3', 'retinanet': 'RetinaNet', 'centernet': 'CenterNet', 'refinedet': 'RefineDet320',
+           'pfpnet': 'PFPNetR'}
+ENGINES = {'ssd300': ['f32', 'f32x3', 'bf16'], 'ssd512': ['f32'], 'yolov3': ['f32'], 'retinanet': ['f32'], 'centernet': ['f32'], 'refinedet': ['f32'],
+           'pfpnet': ['f32']}              # (the last three: the engine test mode defaults to)
+BATCHES = {'ssd300': [1, 8, 32], 'ssd512': [1, 8, 32], 'yolov3': [1, 8, 32], 'retinanet': [1, 8, 16], 'centernet': [1, 8, 32], 'refinedet': [1, 8, 32],
+           'pfpnet': [1, 8, 32]}
+THRESHOLD_KEY = {'centernet': 'score_threshold'}                  # (CenterNet has no NMS: its threshold has a key of its own)
 
 
 def build(name, engine, B, thr, weights=None):
-    cfg, size, _, _ = BCFG.config_of(name, dtype=engine, mode='test', **({} if thr is None else {'nms_score_threshold': thr}))
+    cfg, size, _, _ = BCFG.config_of(name, dtype=engine, mode='test', **({} if thr is None else {THRESHOLD_KEY.get(name, 'nms_score_threshold'): thr}))
     if B is not None:
         cfg['test_batch_size'] = B
     m = getattr(odtk, CLASSES[name])(cfg, None)
@@ -95,10 +99,20 @@ def timed_evaluate(m, gen, n_images, B):
 
 def tail_times(m, name, reps):
     t = m._tail_batched
+    if name == 'centernet':
+        from odtk.centernet import STRIDE as CN_STRIDE
+        out = {'N': t.N, 'pixels_per_image': t.H * t.W, 'top_k': t.K}
+        out['decode_ms'] = events_ms(lambda: t.launch(m.keypoints, m.offset, m.size, m.score_threshold, CN_STRIDE), reps)     # score / arg-max + peak test + top-k
+        out['read_back_ms'] = 1e3 * wall(lambda: t.read(), reps)
+        out['read_back_bytes'] = int(t.words.numel() * 4)
+        return out
     iou = m.nms_iou_threshold
     cand = t.cand.view(torch.uint8)
     out = {'N': t.N, 'rows_per_image': t.A, 'compaction': bool(t.compact)}
-    if name in ('ssd300', 'ssd512'):
+    if name in ('refinedet', 'pfpnet'):
+        out['decode_ms'] = events_ms(lambda: ops.refinedet_decode_batched(m.arm_loc, m.arm_conf, m.odm_loc, m.odm_conf, m.anc[2], m.anc[3], m.nms_score_threshold,
+                                                                           t.conf, t.boxes, t.keep, t.cand), reps)
+    elif name in ('ssd300', 'ssd512'):
         out['decode_ms'] = events_ms(lambda: ops.ssd_decode_batched(m.pred, m.num_classes, m.pri[2], m.pri[3], m.nms_score_threshold, t.conf, t.boxes, t.keep,
                                                                       t.cand), reps)
     elif name == 'retinanet':
@@ -129,7 +143,7 @@ def run(name, engine, a):
     images = (torch.rand(n_img, size, size, 3, generator=g) * 255).round().numpy()
     gt = BCFG.synthetic_gt(n_img, size, 12).numpy()
     gen = [(images[s: s + 8], gt[s: s + 8]) for s in range(0, n_img, 8)]
-    row = {'class': name, 'engine': engine, 'input': size, 'images': n_img, 'score_threshold': one.nms_score_threshold}
+    row = {'class': name, 'engine': engine, 'input': size, 'images': n_img, 'score_threshold': getattr(one, THRESHOLD_KEY.get(name, 'nms_score_threshold'))}
 
     def loop():
         for k in range(n_img):
