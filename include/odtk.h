@@ -21,6 +21,7 @@
 #ifndef ODTK_H_
 #define ODTK_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -692,6 +693,61 @@ long long odtk_voc_eval_workspace_bytes(int num_det, int num_gt, int num_images,
 int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
                   const int* gt_img, int num_gt, int num_images, int num_classes, float iou_thr, int metric, void* workspace,
                   unsigned char* tp_out, int* npos_out, double* ap_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * JPEG (csrc/jpeg.hip, csrc/jpeg_host.h): what tf.image.decode_jpeg(channels=3) does for tfrecord_voc_utils.parse_function, split where the work
+ * changes kind.  HOST, no GPU call, callable from several threads at once: marker parsing and baseline Huffman decoding (SOF0, SOF1 with 8-bit
+ * samples; DC prediction, restart intervals, 0xff00 stuffing, 8- and 16-bit DQT, several tables per DHT / DQT segment).  DEVICE: dequantisation, inverse
+ * DCT, chroma upsampling, colour conversion, crop, for a batch of pictures of different sizes and samplings.
+ * NOT supported, each refused with a message in odtk_last_error(): progressive (SOF2), arithmetic coding, lossless / hierarchical, 12-bit samples,
+ * 4 components (CMYK), RGB-coded files (no JFIF marker and an Adobe marker with transform 0, or component ids 'R', 'G', 'B': libjpeg's rules), sampling other than 1x1 / 2x1 / 2x2 luma over 1x1 chroma, scans that are not the one interleaved scan of all components, a
+ * missing table, a truncated or corrupt stream.  No input makes the host functions read or write outside the buffers handed in.
+ *
+ * Coefficient layout (int16, NOT dequantised, de-zigzagged = natural order, row v of a block at [8 v .. 8 v + 7]): component after component (Y, Cb, Cr),
+ * each component's blocks in raster order of ITS padded block grid blocks_w[c] x blocks_h[c] = (mcu_w * hsamp[c]) x (mcu_h * vsamp[c]), 64 values per
+ * block; component c starts at coef_offset[c], the picture needs coef_count values.  One grayscale component counts as 1x1 whatever its factors say.
+ * qtables: uint16 [4][64], natural order, tables the stream does not define filled with 1.
+ * ------------------------------------------------------------------------- */
+struct odtk_jpeg_info {
+    int width, height, ncomp;          /* ncomp: 1 or 3 */
+    int hsamp[3], vsamp[3], tq[3];     /* sampling factors and quantisation-table index per component */
+    int mcu_w, mcu_h;                  /* MCU grid: columns, rows; an MCU is 8 hsamp[0] x 8 vsamp[0] pixels */
+    int blocks_w[3], blocks_h[3];      /* padded block grid per component */
+    int blocks[3];                     /* = blocks_w * blocks_h */
+    int restart_interval;              /* MCUs between restart markers, 0 = none */
+    long long coef_offset[3];
+    long long coef_count;              /* 64 * (blocks[0] + blocks[1] + blocks[2]) */
+};      /* (no typedef: the function below carries the same name, the struct lives in the tag namespace) */
+int odtk_jpeg_info(const void* data, size_t nbytes, struct odtk_jpeg_info* info);
+int odtk_jpeg_entropy_decode(const void* data, size_t nbytes, int16_t* coef, size_t coef_capacity, uint16_t* qtables);
+/* One plan per picture, in DEVICE memory for the launch; odtk_jpeg_plan_init (host) fills one from the picture's info so that the geometry the kernels
+ * trust is the geometry the parser derived.  coef / qtables as written by odtk_jpeg_entropy_decode and copied to the device (coef 8-byte aligned); planes:
+ * coef_count bytes of scratch (16-byte aligned) that receive the reconstructed sample planes, same block grids, row pitch 8 * blocks_w[c]; out: u8
+ * [height][width][3] (4-byte aligned).  unit_start / px_start: running sums over the batch, in plan order, of units (16 blocks each) and pixel tiles
+ * (1024 pixels each); the kernels' grids run over (picture, unit) and (picture, tile) found from them, so one large picture among many small ones is
+ * spread over the same workgroups as the rest.  Returns the plan's own unit_count / tile_count through the struct. */
+typedef struct odtk_jpeg_plan {
+    const int16_t* coef;
+    const uint16_t* qtables;
+    unsigned char* planes;
+    unsigned char* out;
+    int width, height, ncomp;
+    int hs, vs;                        /* luma sampling factors (chroma is 1x1) */
+    int tq[3];
+    int blocks_w[3], blocks_h[3];
+    int block_start[4];                /* first block of each component in the picture's block sequence; [ncomp] = total */
+    int unit_start, unit_count;        /* IDCT work units: 16 consecutive blocks of the sequence */
+    int tile_start, tile_count;        /* output tiles: 1024 consecutive pixels of the height * width raster */
+} odtk_jpeg_plan;
+int odtk_jpeg_plan_init(odtk_jpeg_plan* plan, const struct odtk_jpeg_info* info, const void* coef_dev, const void* qtables_dev, void* planes_dev, void* out_dev,
+                        int unit_start, int tile_start);
+/* Numerics (the contract the CPU emulation and the device share bit for bit): coefficient * table entry in integers; the 8x8 inverse DCT from its
+ * definition in float32, separable (rows, then columns), basis 0.5 C(u) cos((2x + 1) u pi / 16) as float32 constants, sums in index order, no fused
+ * multiply-add; rint, + 128, clamp to [0, 255].  Chroma: libjpeg's "fancy" triangle filter per axis (3/4 nearer + 1/4 farther sample; at the border of
+ * the component's TRUE size ceil(width / hs) x ceil(height / vs) the missing neighbour is the border sample itself), kept in float32 (exact sixteenths).
+ * R = Y + 1.402 (Cr - 128), G = Y - 0.344136 (Cb - 128) - 0.714136 (Cr - 128), B = Y + 1.772 (Cb - 128) in float32, rint once, clamp.  Grayscale is
+ * replicated to three channels.  Two launches on `stream`; N >= 1; the plans must stay alive until they have run. */
+int odtk_jpeg_reconstruct(const odtk_jpeg_plan* plans_dev, int N, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Collectives (SURVEY.md 8b's export list, 8e): the gradient sum of the data-parallel step for a binder that is not PyTorch.  No reference

@@ -10,7 +10,7 @@ from . import _lib                      # noqa: F401
 from ._lib import BF16, F32, F32X3, OdtkError  # noqa: F401
 
 __all__ = ["BF16", "F32", "OdtkError", "SSD300", "YOLOv3", "RetinaNet", "FCOS", "CenterNet", "SSD512", "RefineDet320", "PFPNetR", "YOLOv2", "LHRCNN",
-           "VOCEvaluator", "evaluate"]
+           "VOCEvaluator", "evaluate", "get_generator", "dataset2tfrecord", "JpegBatchDecoder", "VOC_CLASSES"]
 
 
 def __getattr__(name):
@@ -47,4 +47,7 @@ def __getattr__(name):
     if name in ("VOCEvaluator", "evaluate"):
         from . import voc_eval
         return getattr(voc_eval, name)
+    if name in ("get_generator", "dataset2tfrecord", "xml_to_example", "JpegBatchDecoder", "VOC_CLASSES", "classname_to_ids"):
+        from . import voc_data
+        return getattr(voc_data, name)
     raise AttributeError(name)

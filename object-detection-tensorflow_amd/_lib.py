@@ -32,6 +32,20 @@ class AugPlan(C.Structure):
                 [(n, C.c_float) for n in ("brightness", "contrast", "hue", "angle", "ratio_y", "ratio_x")])
 
 
+class JpegInfo(C.Structure):
+    """Mirror of `struct odtk_jpeg_info` (include/odtk.h)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("ncomp", C.c_int), ("hsamp", C.c_int * 3), ("vsamp", C.c_int * 3), ("tq", C.c_int * 3),
+                ("mcu_w", C.c_int), ("mcu_h", C.c_int), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("blocks", C.c_int * 3),
+                ("restart_interval", C.c_int), ("coef_offset", C.c_longlong * 3), ("coef_count", C.c_longlong)]
+
+
+class JpegPlan(C.Structure):
+    """Mirror of `odtk_jpeg_plan` (include/odtk.h); filled by odtk_jpeg_plan_init only."""
+    _fields_ = [("coef", C.c_void_p), ("qtables", C.c_void_p), ("planes", C.c_void_p), ("out", C.c_void_p), ("width", C.c_int), ("height", C.c_int),
+                ("ncomp", C.c_int), ("hs", C.c_int), ("vs", C.c_int), ("tq", C.c_int * 3), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3),
+                ("block_start", C.c_int * 4), ("unit_start", C.c_int), ("unit_count", C.c_int), ("tile_start", C.c_int), ("tile_count", C.c_int)]
+
+
 class OdtkError(RuntimeError):
     pass
 
@@ -168,6 +182,10 @@ SIGNATURES = {
     "odtk_comm_destroy": (_i, [_vp]),
     "odtk_voc_eval_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "odtk_voc_eval": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_jpeg_info": (_i, [_vp, C.c_size_t, C.POINTER(JpegInfo)]),
+    "odtk_jpeg_entropy_decode": (_i, [_vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "odtk_jpeg_plan_init": (_i, [C.POINTER(JpegPlan), C.POINTER(JpegInfo), _vp, _vp, _vp, _vp, _i, _i]),
+    "odtk_jpeg_reconstruct": (_i, [_vp, _i, _vp]),
 }
 
 _lib = None

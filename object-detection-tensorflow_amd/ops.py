@@ -765,3 +765,33 @@ def voc_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_c
     e = lambda t: _p(t) if t.numel() else None      # noqa: E731 -- an empty side passes NULL
     call("odtk_voc_eval", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), G, int(num_images), int(num_classes),
          float(iou_thr), VOC_METRICS[metric], _p(ws), e(tp), _p(npos), _p(ap), _stream())
+
+
+# ---- JPEG (include/odtk.h, "JPEG"; the loader around these: voc_data.py)
+def jpeg_info(data: bytes):
+    """host only: the picture's geometry as a _lib.JpegInfo; OdtkError with the parser's message for what the decoder does not support"""
+    lib = _lib.load()
+    info = _lib.JpegInfo()
+    if lib.odtk_jpeg_info(data, len(data), C.byref(info)) != 0:
+        raise _lib.OdtkError(f"libodtk error: {lib.odtk_last_error().decode()}")
+    return info
+
+
+def jpeg_entropy_decode(data: bytes, coef, qtables):
+    """host only: Huffman-decode into the numpy arrays coef (int16, >= coef_count elements) and qtables (uint16 [4, 64])"""
+    assert coef.dtype.name == 'int16' and coef.flags['C_CONTIGUOUS'] and qtables.dtype.name == 'uint16' and qtables.size == 256 and qtables.flags['C_CONTIGUOUS']
+    lib = _lib.load()
+    if lib.odtk_jpeg_entropy_decode(data, len(data), coef.ctypes.data, coef.size, qtables.ctypes.data) != 0:
+        raise _lib.OdtkError(f"libodtk error: {lib.odtk_last_error().decode()}")
+
+
+def jpeg_plan_init(plan, info, coef_addr, qt_addr, planes_addr, out_addr, unit_start, tile_start):
+    """host only: fill one _lib.JpegPlan from the picture's info and its device addresses"""
+    lib = _lib.load()
+    if lib.odtk_jpeg_plan_init(C.byref(plan), C.byref(info), coef_addr, qt_addr, planes_addr, out_addr, int(unit_start), int(tile_start)) != 0:
+        raise _lib.OdtkError(f"libodtk error: {lib.odtk_last_error().decode()}")
+
+
+def jpeg_reconstruct(plans_dev, N):
+    """plans_dev: u8 device tensor holding N odtk_jpeg_plan; dequantise, IDCT, upsample, convert and crop all N pictures on the current stream"""
+    call("odtk_jpeg_reconstruct", _p(plans_dev), int(N), _stream())

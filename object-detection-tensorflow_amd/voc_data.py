@@ -1,0 +1,451 @@
+"""PASCAL VOC input: the reference's `utils/tfrecord_voc_utils.py` behind the same names, without TensorFlow.
+
+    dataset2tfrecord / xml_to_example   VOC annotations + JPEG files -> `.tfrecord` shards (the reference's tf.train.Example: three bytes_list features,
+                                        `image` the JPEG file, `shape` int32[3] h, w, depth, `ground_truth` float32[G, 5] ymin, ymax, xmin, xmax, class)
+    TFRecordWriter / tf_record_iterator the record framing (u64 length, masked CRC32C of it, payload, masked CRC32C of the payload)
+    JpegBatchDecoder                    JPEG byte strings -> u8 [h, w, 3] device tensors: Huffman decoding on CPU threads (libodtk, the GIL released),
+                                        everything per block and per pixel in one odtk_jpeg_reconstruct on the device (include/odtk.h, "JPEG")
+    get_generator                       shards -> shuffle buffer -> batches -> decode -> odtk.augment.Augmentor: the object a model takes as
+                                        data_provider['train_generator'] (or 'val_generator', with a config that has no random part)
+
+Where this differs from the reference, on purpose:
+  - dataset2tfrecord writes EVERY annotation.  The reference's shard size `int(ceil(len(xmllist)) / float(total_shards))` rounds down and silently drops
+    up to total_shards - 1 annotations at the end of the list.
+  - get_generator returns ONE re-iterable object instead of (init_op, iterator): every iter() restarts the stream, which is what running init_op did.
+  - Baseline JPEG only (what VOC's JPEGImages are): progressive files, arithmetic coding, CMYK and 12-bit samples are refused with the record's index
+    and the decoder's message.  The ImageNet records of tfrecord_imagenet_utils.py are out of scope.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import glob
+import os
+import queue
+import struct
+import threading
+import warnings
+import weakref
+import xml.etree.ElementTree as ET
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import JpegInfo, JpegPlan, OdtkError
+from .tf_checkpoint import _pb_bytes, _pb_parse, crc32c, mask_crc
+
+VOC_CLASSES = ('aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable', 'dog', 'horse', 'motorbike',
+               'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor')
+classname_to_ids = {name: i for i, name in enumerate(VOC_CLASSES)}
+
+
+# --------------------------------------------------------------------------------------------------- TFRecord framing
+class TFRecordError(ValueError):
+    pass
+
+
+class TFRecordWriter:
+    def __init__(self, path):
+        self.path = path
+        self._f = open(path, 'wb')
+
+    def write(self, record: bytes):
+        head = struct.pack('<Q', len(record))
+        self._f.write(head + struct.pack('<I', mask_crc(crc32c(head))) + record + struct.pack('<I', mask_crc(crc32c(record))))
+
+    def close(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def tf_record_iterator(path, verify=True):
+    """the payloads of one `.tfrecord` file in order; a short record or (verify=True) a bad CRC raises TFRecordError naming the record's byte offset"""
+    with open(path, 'rb') as f:
+        offset, size = 0, os.fstat(f.fileno()).st_size
+        while True:
+            head = f.read(12)
+            if not head:
+                return
+            if len(head) < 12:
+                raise TFRecordError(f'{path}: truncated record header at byte offset {offset} ({len(head)} of 12 bytes)')
+            (length,), (lcrc,) = struct.unpack('<Q', head[:8]), struct.unpack('<I', head[8:])
+            if verify and mask_crc(crc32c(head[:8])) != lcrc:
+                raise TFRecordError(f'{path}: corrupt record at byte offset {offset} (length CRC mismatch)')
+            left = max(size - offset - 12, 0)                # (the length is checked against the file before anything of that size is asked for)
+            if length + 4 > left:
+                raise TFRecordError(f'{path}: truncated record at byte offset {offset} (payload of {length} bytes + CRC, {left} bytes left)')
+            body = f.read(length + 4)
+            if len(body) < length + 4:
+                raise TFRecordError(f'{path}: truncated record at byte offset {offset} (payload of {length} bytes + CRC, {len(body)} bytes read)')
+            payload = body[:length]
+            if verify and mask_crc(crc32c(payload)) != struct.unpack('<I', body[length:])[0]:
+                raise TFRecordError(f'{path}: corrupt record at byte offset {offset} (payload CRC mismatch)')
+            yield payload
+            offset += 16 + length
+
+
+# --------------------------------------------------------------------------------------------------- tf.train.Example
+def _feature(key: str, value: bytes) -> bytes:
+    """one entry of Features.feature (map<string, Feature>): key = 1, value = 2 -> Feature{bytes_list = 1 -> BytesList{value = 1}}"""
+    return _pb_bytes(1, key.encode()) + _pb_bytes(2, _pb_bytes(1, _pb_bytes(1, value)))
+
+
+def encode_example(image: bytes, shape, ground_truth) -> bytes:
+    """the reference's Example (tfrecord_voc_utils.xml_to_example): Example{features = 1 -> Features{feature = 1 (repeated map entry)}}"""
+    shape = np.asarray(shape, np.int32).reshape(3)
+    gt = np.asarray(ground_truth, np.float32).reshape(-1, 5)
+    entries = [_feature('image', bytes(image)), _feature('shape', shape.tobytes()), _feature('ground_truth', gt.tobytes())]
+    return _pb_bytes(1, b''.join(_pb_bytes(1, e) for e in entries))
+
+
+def parse_example(record: bytes) -> dict:
+    """{'image': bytes, 'shape': int32[3], 'ground_truth': float32[G, 5]}; map entries in any order, unknown features ignored"""
+    feats = {}
+    for f, wt, features in _pb_parse(record):
+        if f != 1 or wt != 2:
+            continue
+        for f2, wt2, entry in _pb_parse(features):
+            if f2 != 1 or wt2 != 2:
+                continue
+            key = value = None
+            for f3, wt3, v in _pb_parse(entry):
+                if f3 == 1 and wt3 == 2:
+                    key = v.decode('utf-8', 'replace')
+                elif f3 == 2 and wt3 == 2:
+                    value = v
+            if key in ('image', 'shape', 'ground_truth') and value is not None:
+                for f4, wt4, blist in _pb_parse(value):
+                    if f4 == 1 and wt4 == 2:                      # bytes_list
+                        vals = [v for f5, wt5, v in _pb_parse(blist) if f5 == 1 and wt5 == 2]
+                        if vals:
+                            feats[key] = vals[0]
+    missing = [k for k in ('image', 'shape', 'ground_truth') if k not in feats]
+    if missing:
+        raise ValueError(f'Example without the bytes_list feature(s) {missing}')
+    if len(feats['shape']) != 12 or len(feats['ground_truth']) % 20:
+        raise ValueError(f"Example with a shape of {len(feats['shape'])} bytes / ground truth of {len(feats['ground_truth'])} bytes (int32[3] / float32[G, 5])")
+    return {'image': feats['image'], 'shape': np.frombuffer(feats['shape'], np.int32).copy(),
+            'ground_truth': np.frombuffer(feats['ground_truth'], np.float32).reshape(-1, 5).copy()}
+
+
+# --------------------------------------------------------------------------------------------------- VOC annotations
+def xml_to_example(xmlpath, imgpath) -> bytes:
+    """one VOC annotation + its JPEG file (read, not decoded) -> serialized Example.  Like the reference's xpath('//object') this takes EVERY `object`
+    element of the document, at any depth; the box is the object's own `bndbox` child."""
+    root = ET.parse(xmlpath).getroot()
+    with open(os.path.join(imgpath, root.find('filename').text), 'rb') as f:
+        image = f.read()
+    size = root.find('size')
+    shape = [int(size.find(k).text) for k in ('height', 'width', 'depth')]
+    rows = []
+    for obj in root.iter('object'):
+        box = obj.find('bndbox')
+        rows.append([float(box.find(k).text) for k in ('ymin', 'ymax', 'xmin', 'xmax')] + [classname_to_ids[obj.find('name').text]])
+    return encode_example(image, shape, np.asarray(rows, np.float32).reshape(-1, 5))
+
+
+def dataset2tfrecord(xml_dir, img_dir, output_dir, name, total_shards=5):
+    """Converts a VOC directory: the `*.xml` annotations of xml_dir, in sorted order, with their pictures from img_dir, into total_shards record files
+    `<name>_<k>-of-<n>.tfrecord` (k from 1, both five digits: the reference's file names) under output_dir; returns the paths in shard order.
+    ALL annotations are written: consecutive runs of ceil(n / total_shards), so the last shards may be short or empty (the reference's arithmetic rounds
+    down and drops up to total_shards - 1 annotations, see the module docstring).  Records are added to a directory that already holds files; a warning
+    says so."""
+    total_shards = int(total_shards)
+    if total_shards < 1:
+        raise ValueError(f'total_shards must be >= 1, not {total_shards}')
+    os.makedirs(output_dir, exist_ok=True)
+    if os.listdir(output_dir):
+        warnings.warn(f'dataset2tfrecord: {output_dir} already holds files; the shards are written next to them')
+    annotations = sorted(glob.glob(os.path.join(xml_dir, '*.xml')))
+    run = -(-len(annotations) // total_shards)
+    paths = [os.path.join(output_dir, f'{name}_{k + 1:05d}-of-{total_shards:05d}.tfrecord') for k in range(total_shards)]
+    for k, path in enumerate(paths):
+        with TFRecordWriter(path) as writer:
+            for annotation in annotations[k * run: (k + 1) * run]:
+                writer.write(xml_to_example(annotation, img_dir))
+    return paths
+
+
+# --------------------------------------------------------------------------------------------------- JPEG
+class JpegError(OdtkError):
+    pass
+
+
+def _align(n, a=16):
+    return (n + a - 1) // a * a
+
+
+class HostBatch:
+    """what the CPU half leaves for the device half: per picture its info and offsets, one int16 coefficient array, one uint16 table array"""
+    __slots__ = ('infos', 'coef_off', 'coef', 'qt', 'coef_elems')
+
+
+class JpegBatchDecoder:
+    """decoder(list of JPEG byte strings) -> list of u8 [h, w, 3] tensors on `device`.
+    entropy() is the CPU half (no GPU call: safe on a worker thread), reconstruct() the device half on the current stream; __call__ runs both and lets
+    the Huffman decoder write straight into the pinned staging buffer.  Staging and device buffers grow and never shrink.
+    max_pixels bounds width * height of one picture as its header declares it (default 64 Mi, far above any VOC picture): buffers are sized from the
+    header before a byte of entropy data is checked, and a hostile 65535 x 65535 frame header would otherwise ask for 13 GB."""
+
+    def __init__(self, device='cuda:0', threads=None, max_pixels=1 << 26):
+        self.device = torch.device(device)
+        self.max_pixels = int(max_pixels)
+        self.threads = int(threads) if threads else min(16, len(os.sched_getaffinity(0)))
+        self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix='odtk-jpeg')
+        self._stage = self._dev_in = self._planes = None
+        self._copied = None
+
+    # ---- CPU half
+    def _layout(self, datas):
+        lib = _lib.load()
+        infos, offs, total = [], [], 0
+        for i, d in enumerate(datas):
+            info = JpegInfo()
+            if lib.odtk_jpeg_info(d, len(d), C.byref(info)) != 0:
+                raise JpegError(f'picture {i}: {lib.odtk_last_error().decode()}')
+            if info.width * info.height > self.max_pixels:
+                raise JpegError(f'picture {i}: jpeg: {info.width} x {info.height} pixels exceed max_pixels = {self.max_pixels}')
+            infos.append(info)
+            offs.append(total)
+            total += _align(int(info.coef_count), 8)            # in int16 elements: every picture starts 16-byte aligned
+        return infos, offs, total
+
+    def _decode_into(self, datas, infos, offs, coef_addr, qt_addr):
+        lib = _lib.load()
+
+        def one(i):
+            rc = lib.odtk_jpeg_entropy_decode(datas[i], len(datas[i]), coef_addr + 2 * offs[i], int(infos[i].coef_count), qt_addr + 512 * i)
+            return None if rc == 0 else lib.odtk_last_error().decode()          # (thread_local message: read on the thread that made the call)
+        for i, msg in enumerate(self._pool.map(one, range(len(datas)))):
+            if msg is not None:
+                raise JpegError(f'picture {i}: {msg}')
+
+    def entropy(self, datas) -> HostBatch:
+        datas = [bytes(d) for d in datas]
+        hb = HostBatch()
+        hb.infos, hb.coef_off, hb.coef_elems = self._layout(datas)
+        hb.coef = np.empty(max(hb.coef_elems, 1), np.int16)
+        hb.qt = np.empty((len(datas), 4, 64), np.uint16)
+        self._decode_into(datas, hb.infos, hb.coef_off, hb.coef.ctypes.data, hb.qt.ctypes.data)
+        return hb
+
+    # ---- device half
+    def _sizes(self, infos, coef_elems):
+        N = len(infos)
+        qt_at = _align(2 * coef_elems)
+        plan_at = _align(qt_at + 512 * N)
+        return qt_at, plan_at, _align(plan_at + C.sizeof(JpegPlan) * N)
+
+    def _grow(self, nbytes, plane_bytes):
+        cuda = self.device.type == 'cuda'
+        if self._stage is None or self._stage.numel() < nbytes:
+            self._wait_copy()
+            self._stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=cuda)
+            self._dev_in = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self._planes is None or self._planes.numel() < plane_bytes:
+            self._planes = torch.empty(plane_bytes, dtype=torch.uint8, device=self.device)
+
+    def _wait_copy(self):
+        if self._copied is not None:
+            self._copied.synchronize()           # the staging buffer is free again once the last upload has left it
+            self._copied = None
+
+    def _launch(self, infos, coef_off, coef_elems):
+        """staging buffer filled with coefficients and tables -> plans, one upload, one odtk_jpeg_reconstruct"""
+        from . import ops
+        N = len(infos)
+        qt_at, plan_at, nbytes = self._sizes(infos, coef_elems)
+        out_off, out_bytes, plane_off, plane_bytes = [], 0, [], 0
+        for info in infos:
+            out_off.append(out_bytes)
+            out_bytes += _align(info.height * info.width * 3)
+            plane_off.append(plane_bytes)
+            plane_bytes += _align(int(info.coef_count))
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=self.device)
+        base, planes, outp = self._dev_in.data_ptr(), self._planes.data_ptr(), out.data_ptr()
+        plans = (JpegPlan * N)()
+        units = tiles = 0
+        for i, info in enumerate(infos):
+            ops.jpeg_plan_init(plans[i], info, base + 2 * coef_off[i], base + qt_at + 512 * i, planes + plane_off[i], outp + out_off[i], units, tiles)
+            units += plans[i].unit_count
+            tiles += plans[i].tile_count
+        C.memmove(self._stage.data_ptr() + plan_at, C.addressof(plans), C.sizeof(plans))
+        self._dev_in[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)
+        if self.device.type == 'cuda':
+            self._copied = torch.cuda.Event()
+            self._copied.record()
+        ops.jpeg_reconstruct(self._dev_in[plan_at:], N)
+        return [out[o: o + i.height * i.width * 3].view(i.height, i.width, 3) for o, i in zip(out_off, infos)]
+
+    def reconstruct(self, hb: HostBatch):
+        qt_at, plan_at, nbytes = self._sizes(hb.infos, hb.coef_elems)
+        self._grow(nbytes, sum(_align(int(i.coef_count)) for i in hb.infos))
+        self._wait_copy()
+        stage = self._stage.numpy()
+        stage[:2 * hb.coef_elems] = hb.coef[:hb.coef_elems].view(np.uint8)
+        stage[qt_at: qt_at + 512 * len(hb.infos)] = hb.qt.reshape(-1).view(np.uint8)
+        return self._launch(hb.infos, hb.coef_off, hb.coef_elems)
+
+    def __call__(self, datas):
+        datas = [bytes(d) for d in datas]
+        if not datas:
+            return []
+        infos, offs, elems = self._layout(datas)
+        qt_at, plan_at, nbytes = self._sizes(infos, elems)
+        self._grow(nbytes, sum(_align(int(i.coef_count)) for i in infos))
+        self._wait_copy()
+        addr = self._stage.data_ptr()
+        self._decode_into(datas, infos, offs, addr, addr + qt_at)
+        return self._launch(infos, offs, elems)
+
+
+# --------------------------------------------------------------------------------------------------- the generator
+def shuffle_stream(items, buffer_size, rng):
+    """tf.data's shuffle: fill a buffer of buffer_size, then emit a uniformly drawn slot and refill it from the input; when the input ends the drawn
+    slot is refilled with the last one until the buffer is empty.  rng.integers(n) is the only draw, one per emitted item."""
+    buf = []
+    for item in items:
+        if len(buf) < buffer_size:
+            buf.append(item)
+            continue
+        i = int(rng.integers(len(buf)))
+        out, buf[i] = buf[i], item
+        yield out
+    while buf:
+        i = int(rng.integers(len(buf)))
+        out, buf[i] = buf[i], buf[-1]
+        buf.pop()
+        yield out
+
+
+def _records(paths, verify):
+    index = 0
+    for p in paths:
+        for payload in tf_record_iterator(p, verify):
+            yield index, payload
+            index += 1
+
+
+def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop):
+    """CPU work only (file reads, CRCs, protobuf, Huffman decoding): never a GPU call.  Puts (host batch, ground truths) or an exception."""
+    def put(item):
+        while not stop.is_set():
+            try:
+                out_q.put(item, timeout=0.05)
+                return True
+            except queue.Full:
+                pass
+        return False
+    try:
+        rng = np.random.default_rng(seed)
+        while not stop.is_set():                                       # .repeat(): every pass reshuffles with the running generator
+            batch, emitted = [], 0
+            for index, payload in shuffle_stream(_records(paths, verify), buffer_size, rng):
+                if stop.is_set():
+                    return
+                batch.append((index, payload))
+                if len(batch) < batch_size:
+                    continue
+                try:
+                    examples = [parse_example(p) for _, p in batch]
+                except Exception as e:                                 # noqa: BLE001
+                    raise ValueError(f'records {[i for i, _ in batch]}: {e}') from e
+                try:
+                    hb = decoder.entropy([e['image'] for e in examples])
+                except JpegError as e:
+                    pic, _, msg = str(e).partition(': ')
+                    k = int(pic.split()[1]) if pic.startswith('picture ') else 0
+                    raise JpegError(f'record {batch[k][0]}: {msg}') from None
+                if not put((hb, [torch.from_numpy(e['ground_truth']) for e in examples])):
+                    return
+                batch, emitted = [], emitted + 1
+            if emitted == 0:                                           # (drop_remainder with fewer records than a batch: nothing, for ever)
+                raise ValueError(f'the tfrecords hold fewer than batch_size = {batch_size} records')
+    except BaseException as e:                                          # noqa: BLE001 -- handed to the consumer, which raises it
+        put(e)
+
+
+class _VOCIterator:
+    def __init__(self, gen):
+        self._decoder, self._augmentor = gen._decoder, gen._augmentor
+        self._q = queue.Queue(maxsize=max(1, gen.prefetch))
+        self._stop = threading.Event()
+        self._thread = threading.Thread(target=_worker, name='odtk-voc-loader', daemon=True,
+                                        args=(gen.tfrecords, gen.batch_size, gen.buffer_size, gen.seed, gen.verify, gen._decoder, self._q, self._stop))
+        self._thread.start()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._stop.is_set():
+            raise StopIteration
+        while True:
+            try:
+                item = self._q.get(timeout=0.1)
+                break
+            except queue.Empty:
+                if not self._thread.is_alive() and self._q.empty():
+                    self.close()
+                    raise RuntimeError('the loader thread ended without a result') from None
+        if isinstance(item, BaseException):
+            self.close()
+            raise item
+        hb, gts = item
+        images = self._decoder.reconstruct(hb)             # upload + odtk_jpeg_reconstruct, on the consumer's thread and current stream
+        return self._augmentor(images, gts)
+
+    def close(self):
+        self._stop.set()
+        if self._thread is not threading.current_thread():
+            self._thread.join()
+
+    def __del__(self):
+        try:
+            self._stop.set()
+        except Exception:                                   # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class VOCGenerator:
+    """see get_generator"""
+    endless = True                  # evaluate() asks for num_images (or num_val) before it reads a stream that never ends
+
+    def __init__(self, tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, decoder=None,
+                 augmentor=None):
+        self.tfrecords = [tfrecords] if isinstance(tfrecords, (str, os.PathLike)) else list(tfrecords)
+        self.batch_size, self.buffer_size, self.prefetch, self.verify, self.seed = int(batch_size), max(1, int(buffer_size)), int(prefetch), verify, seed
+        assert self.batch_size > 0 and self.tfrecords
+        if augmentor is None:
+            from .augment import Augmentor
+            augmentor = Augmentor(seed=seed, **image_preprocess_config)
+        self._augmentor = augmentor
+        self._decoder = decoder if decoder is not None else JpegBatchDecoder(device)
+        self._last = None
+
+    def __iter__(self):
+        last = self._last() if self._last is not None else None
+        if last is not None:
+            last.close()                                    # one live stream per generator, like the reference's single re-initialised iterator
+        it = _VOCIterator(self)
+        self._last = weakref.ref(it)
+        return it
+
+
+def get_generator(tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, **hooks):
+    """tfrecord_voc_utils.get_generator: `.tfrecord` shards -> endless batches ([B, H, W, 3] f32 pictures, [B, pad_truth_to, 5] ground truth), exactly what
+    odtk.augment.Augmentor returns with ground truth (image_preprocess_config is the reference's image_augmentor_config and needs pad_truth_to).
+    Order of the stages as in the reference: records in file order -> shuffle buffer of buffer_size (shuffle_stream) -> batches of batch_size, the
+    remainder of a pass dropped -> repeated without end.  Each iter() of the returned object restarts the stream (and ends the previous one).  A daemon
+    thread reads, parses and Huffman-decodes up to `prefetch` batches ahead; upload, reconstruction and augmentation run on the consumer's thread and
+    current stream.  A record whose JPEG the decoder refuses raises JpegError('record <index>: <message>') from next().  `seed` fixes the shuffle and
+    the augmentor's draws.  hooks (tests): decoder=, augmentor= replace the two device stages."""
+    return VOCGenerator(tfrecords, batch_size, buffer_size, image_preprocess_config, device, seed, prefetch, verify, **hooks)

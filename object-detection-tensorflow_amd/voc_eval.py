@@ -178,6 +178,8 @@ def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='
             if nv is None:
                 nv = (getattr(model, 'data_provider', None) or {}).get('num_val')
             num_images = int(nv) if nv and int(nv) > 0 else None
+    if num_images is None and getattr(generator, 'endless', False):
+        raise ValueError("evaluate: this generator repeats without end (voc_data.get_generator): give num_images, or num_val > 0 in the data provider")
     dev = getattr(model, 'dev', None)
     ev = VOCEvaluator(model.config['num_classes'], iou_threshold, metric, device=dev if dev is not None and dev.type == 'cuda' else None)
     if batch_size > 1:
