@@ -194,7 +194,7 @@ int odtk_avgpool2x2_fwd(const void* x, void* y, int N, int H, int W, int ld, int
 int odtk_avgpool2x2_bwd(const void* dy, void* dx, int N, int H, int W, int ld, int dtype, void* stream);
 
 /* y = relu(a + b) on rows with their own pitches (RefineDet's transfer-connection block, RefineDet.py:371), and the gradient of a ReLU taken
- * from its OUTPUT: dx[m][c] (+= when accumulate) = dy[m][c] where y[m][c] > 0.  dy shares y's pitch. */
+ * from its OUTPUT: dx[m][c] (+= when accumulate) = dy[m][c] where y[m][c] > 0.  dy shares y's pitch.  Columns [C, ld) of y / dx are not written. */
 int odtk_add_relu_fwd(const void* a, int lda, const void* b, int ldb, void* y, int ldy, long long M, int C, int dtype, void* stream);
 int odtk_relu_bwd(const void* y, const void* dy, int ldy, void* dx, int lddx, long long M, int C, int dtype, int accumulate, void* stream);
 
@@ -268,7 +268,8 @@ int odtk_bn_bwd_given(const void* z, const void* y, const void* dy, int M, int C
  * channel slice of a concat buffer is an ordinary operand; C and every pitch multiples of 16 bytes, pointers 16-byte aligned.
  * odtk_add2d: y = a + b (b NULL: pitched copy; y may alias a: accumulate) -- `conv = conv + conv2` (YOLOv3.py:489-491),
  * tf.concat halves and their gradients (:412).  odtk_upsample2x_*: tf.image.resize_nearest_neighbor to twice the size
- * (:411) and its gradient (sum of the four copies; accumulate != 0 adds to dx). */
+ * (:411) and its gradient (sum of the four copies; accumulate != 0 adds to dx).  Only the C columns of a row are
+ * written: pad columns [C, ld) of y / dx keep what they held.  y may alias b as well as a when their pitches agree. */
 int odtk_add2d(const void* a, int lda, const void* b, int ldb, void* y, int ldy, long long M, int C, int dtype, void* stream);
 int odtk_upsample2x_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int dtype, void* stream);
 int odtk_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, int N, int H, int W, int C, int dtype, int accumulate,
@@ -313,7 +314,8 @@ int odtk_exp_rows_bwd(const float* dy, const float* y, void* dx, int lddx, int d
 
 /* conv rows <-> the f32 prediction tensors of the box-side kernels: tf.reshape + tf.concat over the pyramid levels
  * (RetinaNet.py:184-186, :321-326).  Row m of image n = m / rows_per_img is read / written at
- * y + n * y_img_stride + (m % rows_per_img) * ldy (floats); x is [M][ldx] in `dtype`; _from_f32 zeroes x's pad columns. */
+ * y + n * y_img_stride + (m % rows_per_img) * ldy (floats); x is [M][ldx] in `dtype`; _from_f32 zeroes x's pad columns, _to_f32 writes only the
+ * C columns of the M rows it is given (the rest of y keeps what it held). */
 int odtk_rows_to_f32(const void* x, int ldx, int dtype, float* y, int ldy, int rows_per_img, long long y_img_stride, long long M, int C,
                      void* stream);
 int odtk_rows_from_f32(const float* y, int ldy, int rows_per_img, long long y_img_stride, void* x, int ldx, int dtype, long long M, int C,
@@ -355,7 +357,8 @@ int odtk_sum_f32(const float* in, long long n, float* out, void* stream);
  * total = scale_a * sum_a + scale_b * sum_b.  sum_a / sum_b may be null.  Fixed summation order. */
 int odtk_loss_total(const float* a, int na, int stride_a, const float* b, long long nb, float scale_a, float scale_b, float* sum_a, float* sum_b,
                     float* total, void* stream);
-/* cast f32 -> dtype */
+/* cast f32 -> dtype (round to nearest even, NaN stays NaN); exactly n elements are written, in and out of any alignment.  n = 0 succeeds, writes nothing
+ * and looks at neither pointer (an empty view has none); the same holds for odtk_cast_to_f32. */
 int odtk_cast_from_f32(const float* in, void* out, long long n, int dtype, void* stream);
 /* cast dtype -> f32 (the bf16 gradient buckets of the data-parallel path are summed by RCCL as bf16 and widened back into the flat f32
  * gradient buffer; replaces nothing in the reference, which is single-device: testSSD300.py:14) */

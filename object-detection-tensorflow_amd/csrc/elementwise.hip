@@ -1774,6 +1774,8 @@ extern "C" int odtk_loss_total(const float* a, int na, int stride_a, const float
 }
 
 extern "C" int odtk_cast_from_f32(const float* in, void* out, long long n, int dtype, void* stream) {
+    ODTK_REQUIRE(n >= 0, "cast: n=%lld", n);
+    if (n == 0) return ODTK_OK;                       // (an empty view has no address: nothing to check, nothing to write)
     ODTK_REQUIRE(in && out, "cast: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == ODTK_BF16 && n >= 8 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0) {
@@ -1790,9 +1792,10 @@ extern "C" int odtk_cast_from_f32(const float* in, void* out, long long n, int d
 }
 
 extern "C" int odtk_cast_to_f32(const void* in, int dtype, float* out, long long n, void* stream) {
-    ODTK_REQUIRE(in && out && n >= 0, "cast: bad argument");
-    hipStream_t st = (hipStream_t)stream;
+    ODTK_REQUIRE(n >= 0, "cast: n=%lld", n);
     if (n == 0) return ODTK_OK;
+    ODTK_REQUIRE(in && out, "cast: null pointer");
+    hipStream_t st = (hipStream_t)stream;
     if (dtype == ODTK_BF16 && n >= 8 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0) {
         const long long n8 = n / 8;
         hipLaunchKernelGGL(cast_bf16_to_f32_x8_kernel, dim3(grid_for(n8, 256)), dim3(256), 0, st, (const uint4*)in, (float4*)out, n8);

@@ -192,8 +192,10 @@ def bn_bwd(z, y, dy, M, C_, ldz, ldy, rows_per_img, y_img_stride, gamma, save_me
 
 
 def add2d(a, lda, b, ldb, y, ldy, M, C_):
-    v = a[:M, :C_].float() + (b[:M, :C_].float() if b is not None else 0.)
-    y[:M, :C_] = v.to(y.dtype)
+    if b is None:                                             # a pitched COPY: bit patterns survive (-0.0 + 0. would come back as +0.0)
+        y[:M, :C_] = a[:M, :C_]
+        return
+    y[:M, :C_] = (a[:M, :C_].float() + b[:M, :C_].float()).to(y.dtype)
 
 
 def upsample2x_fwd(x, ldx, y, ldy, N, H, W, C_):
@@ -261,7 +263,9 @@ def copy_channels(src, lds, src_off, dst, ldd, dst_off, M, C_, accumulate=False,
     v = src[:, src_off: src_off + C_].float()
     if relu_src is not None:
         v = v * (relu_src[:, dst_off: dst_off + C_].float() > 0)
-    dst[:, dst_off: dst_off + C_] = (v + (dst[:, dst_off: dst_off + C_].float() if accumulate else 0.)).to(dst.dtype)
+    if accumulate:                                            # (a plain copy keeps the bit pattern: -0.0 + 0. would come back as +0.0)
+        v = v + dst[:, dst_off: dst_off + C_].float()
+    dst[:, dst_off: dst_off + C_] = v.to(dst.dtype)
 
 
 def _pool(x_nhwc, k, stride, pt, pl, Ho, Wo):

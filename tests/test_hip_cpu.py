@@ -350,52 +350,8 @@ def test_global_batch_norm_entry_points_from_source(shape, dt):
     rows each compute what odtk_bn_fwd / odtk_bn_bwd compute on all rows"""
     import odtk  # noqa: F401
     from odtk import ops
-    M, C, relu = shape
-    tdt = torch.float32 if dt == 'f32' else torch.bfloat16
-    g = torch.Generator().manual_seed(5)
-    z = (torch.randn(2 * M, C, generator=g) * 1.5 + 0.3).to(tdt)
-    dy = torch.randn(2 * M, C, generator=g).to(tdt)
-    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
-    with HC.installed():
-        p = ops._p
-        ws = torch.zeros(ops.bn_workspace_bytes(2 * M, C), dtype=torch.uint8)
-        # one device, all rows
-        mm, mv, sm, si = torch.zeros(C), torch.ones(C), torch.zeros(C), torch.zeros(C)
-        y, dz, dg, db = torch.zeros(2 * M, C, dtype=tdt), torch.zeros(2 * M, C, dtype=tdt), torch.zeros(C), torch.zeros(C)
-        ops.bn_fwd(z, 2 * M, C, C, gamma, beta, mm, mv, sm, si, True, int(relu), y, C, 2 * M, 0, ws)
-        ops.bn_bwd(z, y, dy, 2 * M, C, C, C, 2 * M, 0, gamma, sm, si, int(relu), dz, dg, db, ws)
-        # two replicas
-        zs, dys = [z[:M].clone(), z[M:].clone()], [dy[:M].clone(), dy[M:].clone()]
-        mom = torch.zeros(2, 2, C)
-        for r in range(2):
-            ops.call('odtk_bn_moments', p(zs[r]), M, C, C, ops.dt_of(zs[r]), p(mom[r][0]), p(mom[r][1]), p(ws), None)
-        st = [dict(mm=torch.zeros(C), mv=torch.ones(C), sm=torch.zeros(C), si=torch.zeros(C), y=torch.zeros(M, C, dtype=tdt), dz=torch.zeros(M, C, dtype=tdt),
-                   sums=torch.zeros(2 * C)) for _ in range(2)]
-        for r in range(2):
-            d = st[r]
-            ops.call('odtk_bn_fwd_given', p(zs[r]), M, C, C, ops.dt_of(zs[r]), p(gamma), p(beta), p(mom), 2, p(d['mm']), p(d['mv']), p(d['sm']), p(d['si']),
-                     int(relu), p(d['y']), ops.dt_of(d['y']), C, M, 0, p(ws), None)
-            d['y1'] = y[r * M:(r + 1) * M].clone()          # the ReLU mask of the one-device pass: an activation a rounding away from zero must not flip
-            ops.call('odtk_bn_bwd_sums', p(zs[r]), p(d['y1']), p(dys[r]), M, C, C, ops.dt_of(zs[r]), ops.dt_of(dys[r]), C, M, 0, p(d['sm']), p(d['si']), int(relu),
-                     p(d['sums']), p(ws), None)
-        glob = st[0]['sums'] + st[1]['sums']
-        for r in range(2):
-            d = st[r]
-            ops.call('odtk_bn_bwd_given', p(zs[r]), p(d['y1']), p(dys[r]), M, C, C, ops.dt_of(zs[r]), ops.dt_of(dys[r]), C, M, 0, p(gamma), p(d['sm']), p(d['si']),
-                     int(relu), p(glob), 2 * M, p(d['dz']), p(ws), None)
-    tol = 2e-5 if dt == 'f32' else 2e-2
-
-    def close(a, b, t=tol):
-        assert float((a.float() - b.float()).abs().max()) <= t * (float(b.float().abs().max()) + 1e-6), float((a.float() - b.float()).abs().max())
-    for r in range(2):
-        d = st[r]
-        close(d['sm'], sm, 2e-5); close(d['si'], si, 2e-4); close(d['mm'], mm, 2e-5); close(d['mv'], mv, 2e-4)
-        close(d['y'], y[r * M:(r + 1) * M])
-        close(d['dz'], dz[r * M:(r + 1) * M])
-    if dt == 'f32':                                         # (bf16: a ReLU mask taken from y rounded differently in a few entries moves the sums)
-        close(glob[:C], db, 1e-4); close(glob[C:], dg, 1e-4)
-    else:
-        close(glob[:C], db, 3e-2); close(glob[C:], dg, 3e-2)
+    import glue_exact as GX
+    GX.global_batch_norm_case(ops, CPU, shape, dt, HC.installed())          # (the same body runs on the GPU: tests/test_gpu_glue_exact.py)
 
 
 @pytest.mark.parametrize('dt', ['f32', 'bf16'])
