@@ -698,6 +698,24 @@ int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, c
                   unsigned char* tp_out, int* npos_out, double* ap_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Classification metrics: held-out top-1 / top-k accuracy and cross-entropy over the logits of the pre-training head (csrc/classify.hip; no reference
+ * counterpart).  logits: rows [N][ldl] f32, columns [C, ldl) are padding and never read; labels int32 [N].  Per row n with a label inside [0, C):
+ *   rank[n] = #{j : logit[j] > logit[label]} + #{j < label : logit[j] == logit[label]}   (the lower index first: rank == 0 <=> label == the pred of
+ *             odtk_gap_softmax_ce_fwd, the first index of the maximum); a label logit that is NaN or +-inf gives rank = C (a miss); NaN elsewhere
+ *             compares false and does not count;
+ *   loss[n] = log-sum-exp (shifted by the row maximum, f32, the arithmetic of odtk_gap_softmax_ce_fwd) - logit[label];
+ *   a top-1 hit when rank == 0, a top-k hit when rank < top_k.
+ * A label outside [0, C): rank[n] = -1, loss[n] = NaN, the row counted in totals[3] and nowhere else.
+ * rank and loss are OVERWRITTEN; the others are ACCUMULATED (+=; the caller zeroes them once per evaluation):
+ *   totals[4] = rows counted, top-1 hits, top-k hits, rows with a label outside [0, C);  loss_sum[0] += the counted rows' losses, added in f64 in row
+ *   order;  class_seen[c] / class_hit[c] += counted rows / top-1 hits with label c.
+ * Limits: 1 <= C <= 1024, 1 <= top_k <= C, 1 <= N <= 65535, ldl >= C, no NULL pointer; anything else fails with a message naming the value.
+ * Two launches on `stream`, no atomics on global memory: bit-identical from run to run.  The accumulators belong to one stream at a time.
+ * ------------------------------------------------------------------------- */
+int odtk_classify_eval(const float* logits, int ldl, int N, int C, const int* labels, int top_k, int* rank, float* loss, long long* totals,
+                       double* loss_sum, int* class_seen, int* class_hit, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * JPEG (csrc/jpeg.hip, csrc/jpeg_host.h): what tf.image.decode_jpeg(channels=3) does for tfrecord_voc_utils.parse_function, split where the work
  * changes kind.  HOST, no GPU call, callable from several threads at once: marker parsing and baseline Huffman decoding (SOF0, SOF1 with 8-bit
  * samples; DC prediction, restart intervals, 0xff00 stuffing, 8- and 16-bit DQT, several tables per DHT / DQT segment).  DEVICE: dequantisation, inverse

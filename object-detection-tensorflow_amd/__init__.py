@@ -10,7 +10,8 @@ from . import _lib                      # noqa: F401
 from ._lib import BF16, F32, F32X3, OdtkError  # noqa: F401
 
 __all__ = ["BF16", "F32", "OdtkError", "SSD300", "YOLOv3", "RetinaNet", "FCOS", "CenterNet", "SSD512", "RefineDet320", "PFPNetR", "YOLOv2", "LHRCNN",
-           "VOCEvaluator", "evaluate", "get_generator", "dataset2tfrecord", "JpegBatchDecoder", "VOC_CLASSES"]
+           "VOCEvaluator", "evaluate", "get_generator", "dataset2tfrecord", "JpegBatchDecoder", "VOC_CLASSES", "ClassificationEvaluator",
+           "get_imagenet_generator", "imagenet_dataset2tfrecord"]
 
 
 def __getattr__(name):
@@ -50,4 +51,13 @@ def __getattr__(name):
     if name in ("get_generator", "dataset2tfrecord", "xml_to_example", "JpegBatchDecoder", "VOC_CLASSES", "classname_to_ids"):
         from . import voc_data
         return getattr(voc_data, name)
+    if name == "ClassificationEvaluator":
+        from .classify_eval import ClassificationEvaluator
+        return ClassificationEvaluator
+    if name == "imagenet_data":
+        import importlib
+        return importlib.import_module(".imagenet_data", __name__)
+    if name in ("get_imagenet_generator", "imagenet_dataset2tfrecord"):
+        from . import imagenet_data
+        return getattr(imagenet_data, {"get_imagenet_generator": "get_generator", "imagenet_dataset2tfrecord": "dataset2tfrecord"}[name])
     raise AttributeError(name)

@@ -767,6 +767,14 @@ def voc_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_c
          float(iou_thr), VOC_METRICS[metric], _p(ws), e(tp), _p(npos), _p(ap), _stream())
 
 
+# ---------------------------------------------------------------- evaluation: classification metrics (csrc/classify.hip)
+def classify_eval(logits, ldl, N, C_, labels, top_k, rank, loss, totals, loss_sum, class_seen, class_hit):
+    """logits f32 rows [N][ldl], labels i32[N] -> rank i32[N], loss f32[N] overwritten; totals i64[4], loss_sum f64[1], class_seen / class_hit i32[C]
+    accumulated (include/odtk.h, "Classification metrics")"""
+    call("odtk_classify_eval", _p(logits), int(ldl), int(N), int(C_), _p(labels), int(top_k), _p(rank), _p(loss), _p(totals), _p(loss_sum),
+         _p(class_seen), _p(class_hit), _stream())
+
+
 # ---- JPEG (include/odtk.h, "JPEG"; the loader around these: voc_data.py)
 def jpeg_info(data: bytes):
     """host only: the picture's geometry as a _lib.JpegInfo; OdtkError with the parser's message for what the decoder does not support"""

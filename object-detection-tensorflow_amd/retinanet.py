@@ -12,7 +12,8 @@ Reference: /root/reference/RetinaNet.py -- the DETECTION graph (`is_pretraining:
 The classification pre-training graph (`is_pretraining: True`, :61-99, :120-135, :476-531, :548-551) is built behind the same class:
   * the backbone alone (l0 .. l64), the LAST unit's sum (no batch norm / ReLU after it) -> global average pool -> softmax cross-entropy
     (odtk_gap_softmax_ce_fwd / _bwd): 4 * FILTERS[-1] = 224 logits, no dense layer, config['num_classes'] plays no part; labels int [N] in [0, 224)
-  * train_one_epoch -> (mean loss, mean accuracy); test_one_image -> pred int64 [1]; save_weight -> the 260 trainables of 'feature_extractor'
+  * train_one_epoch -> (mean loss, mean accuracy); test_one_image -> pred int64 [1]; test_images -> pred int64 [n]; save_weight -> the 260
+    trainables of 'feature_extractor'; evaluate -> held-out top-1 / top-k / loss with BATCH statistics (_evaluate_pretraining, classify_eval.py)
   * the moving statistics are NEVER updated (the pre-training train_op has no UPDATE_OPS dependency, :134): they stay 0 / 1, test mode uses them
 Same conventions as yolov3.py: layers l0 .. l121 in creation order (layer k = conv k + batch norm k; l0 is conv -> BN -> ReLU, every
 other layer BN -> ReLU -> conv with a LIVE bias gradient), one flat f32 parameter buffer, NHWC rows with zero-filled pad columns for
@@ -435,7 +436,7 @@ class RetinaNet(EvaluateMixin, DetectorBase):
         NMS takes per problem: odtk_compact_rows + odtk_gather_rows, the place torch.nonzero holds in the single-image path) -> odtk_nms_image_class ->
         odtk_detection_pack -> one read-back.  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
         if self.is_pretraining:
-            raise ValueError("test_images: a classification pre-training model has no detections")
+            return self._test_pretraining_images(images)
         n = self._stage_test_images(images)
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
         N, A, nc = self.batch_size, self.pconf.shape[1], self.num_classes - 1
@@ -448,6 +449,13 @@ class RetinaNet(EvaluateMixin, DetectorBase):
             t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
         ops.retina_decode_batched(self.pconf, self.pbox, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
         return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
+
+    def evaluate(self, num_images=None, generator=None, **kw):
+        """detection graph: VOC mAP (voc_eval.EvaluateMixin.evaluate).  Pre-training graph: held-out accuracy, see _evaluate_pretraining
+        (keyword: top_k = 5)."""
+        if self.is_pretraining:
+            return self._evaluate_pretraining(num_images, generator, **kw)
+        return super().evaluate(num_images, generator, **kw)
 
     def test_one_image(self, images):
         if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
@@ -620,8 +628,65 @@ class RetinaNet(EvaluateMixin, DetectorBase):
             sys.stdout.write('\n')
         return np.mean(mean_loss), np.mean(mean_acc)
 
+    def _evaluate_pretraining(self, num_images=None, generator=None, top_k=5):
+        """Held-out top-1 / top-k accuracy and mean cross-entropy of the pre-training graph over `generator`: batches (images [B, H, W, 3], labels [B]),
+        the set_batch contract, or an (initializer, iterator) pair.  Defaults: the data provider's val_generator and num_val (when > 0); a generator
+        that repeats without end needs a count.  Returns ClassificationEvaluator.result(): {'num_images', 'top1', 'topk', 'top_k', 'loss',
+        'class_seen', 'class_accuracy', 'invalid_labels'}.
+
+        BATCH STATISTICS, on a TRAIN-mode model: as in the reference, this graph never updates its moving statistics (the pre-training train_op has no
+        UPDATE_OPS dependency, RetinaNet.py:134; _bn_relu) -- they stay 0 / 1 for the whole run, so a test-mode forward pass classifies at chance
+        whatever the weights are.  Held-out accuracy is therefore computed the way the reference computes its training accuracy: set_batch, then the
+        training-mode forward pass (batch statistics, whose moving-average update goes to a throwaway scratch), then odtk_classify_eval on the logits.
+        Nothing else runs: no backward pass, no optimizer step -- P, Mom, S and global_step are bit-identical afterwards.  It follows that every batch
+        must hold exactly batch_size images (another size raises ValueError) and that num_images is rounded DOWN to whole batches; 'num_images' of
+        the result is the count actually evaluated.  A test-mode pre-training model cannot be evaluated and says so."""
+        from .classify_eval import ClassificationEvaluator
+        from .voc_eval import _batches
+        if self.mode != 'train':
+            raise ValueError("evaluate: a test-mode pre-training model normalises with its moving statistics, which the pre-training graph never updates "
+                             "(they are 0 / 1): it classifies at chance whatever the weights.  Call evaluate() on the train-mode model (batch statistics)")
+        if generator is None:
+            generator = getattr(self, 'val_generator', None)
+            if generator is None:
+                raise ValueError("evaluate: no generator given and the data provider has no val_generator")
+            if num_images is None:
+                nv = getattr(self, 'num_val', 0)
+                num_images = int(nv) if nv and int(nv) > 0 else None
+        if num_images is None and getattr(generator, 'endless', False):
+            raise ValueError("evaluate: this generator repeats without end (voc_data.get_generator): give num_images, or num_val > 0 in the data provider")
+        B = self.batch_size
+        batches = None if num_images is None else int(num_images) // B
+        if batches is not None and batches < 1:
+            raise ValueError(f"evaluate: num_images = {num_images} is less than one batch of batch_size = {B} images")
+        ev = self._classify_evaluator = ClassificationEvaluator(self.feat.C, top_k, device=self.dev)
+        done = 0
+        for images, labels in _batches(generator):
+            if images.shape[0] != B:
+                raise ValueError(f"evaluate: a batch of {images.shape[0]} images: the pre-training graph is evaluated with batch statistics at batch_size = "
+                                 f"{B} (drop the remainder)")
+            self.set_batch(images, labels)
+            self._forward(True)
+            ev.update(self.logits, self.labels)
+            done += 1
+            if batches is not None and done >= batches:
+                break
+        r = ev.result()
+        if r['invalid_labels'] > 0:
+            raise ValueError(f"evaluate: {r['invalid_labels']} labels outside [0, {self.feat.C})")
+        return r
+
+    def _test_pretraining_images(self, images):
+        """test_images of a test-mode pre-training model: n <= test_batch_size images in one forward pass at N = test_batch_size -> the predicted
+        classes, int64 [n] (moving statistics 0 / 1 as in the reference: see _evaluate_pretraining for held-out accuracy)"""
+        n = self._stage_test_images(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        return self.pred[:n].cpu().numpy().astype(np.int64)
+
     def _test_one_pretraining_image(self, images):
         """RetinaNet.py:501-503: the predicted class, int64 [1] (the fed tensor bypasses the mean subtraction unless test_subtract_mean)"""
+        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
+            return self._test_pretraining_images(images)
         images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
         if self.data_format == 'channels_first' and images.shape[1] == 3:
             images = images.permute(0, 2, 3, 1)

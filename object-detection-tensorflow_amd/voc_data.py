@@ -13,7 +13,9 @@ Where this differs from the reference, on purpose:
     up to total_shards - 1 annotations at the end of the list.
   - get_generator returns ONE re-iterable object instead of (init_op, iterator): every iter() restarts the stream, which is what running init_op did.
   - Baseline JPEG only (what VOC's JPEGImages are): progressive files, arithmetic coding, CMYK and 12-bit samples are refused with the record's index
-    and the decoder's message.  The ImageNet records of tfrecord_imagenet_utils.py are out of scope.
+    and the decoder's message.
+The ImageNet records of tfrecord_imagenet_utils.py (one label per picture) are imagenet_data.py: it shares the framing, the decoder, the Example map
+reader (_example_features) and the loader thread (_worker / _VOCIterator, given its own "parse" and "payload" functions: _worker's parse= / extra=) with this file.
 """
 from __future__ import annotations
 
@@ -106,9 +108,9 @@ def encode_example(image: bytes, shape, ground_truth) -> bytes:
     return _pb_bytes(1, b''.join(_pb_bytes(1, e) for e in entries))
 
 
-def parse_example(record: bytes) -> dict:
-    """{'image': bytes, 'shape': int32[3], 'ground_truth': float32[G, 5]}; map entries in any order, unknown features ignored"""
-    feats = {}
+def _example_features(record: bytes):
+    """the (key, serialized Feature) entries of Example{features = 1 -> Features{feature = 1 (repeated map entry: key = 1, value = 2)}}, in record order;
+    an entry without a value comes with None.  Shared with imagenet_data.py."""
     for f, wt, features in _pb_parse(record):
         if f != 1 or wt != 2:
             continue
@@ -121,12 +123,19 @@ def parse_example(record: bytes) -> dict:
                     key = v.decode('utf-8', 'replace')
                 elif f3 == 2 and wt3 == 2:
                     value = v
-            if key in ('image', 'shape', 'ground_truth') and value is not None:
-                for f4, wt4, blist in _pb_parse(value):
-                    if f4 == 1 and wt4 == 2:                      # bytes_list
-                        vals = [v for f5, wt5, v in _pb_parse(blist) if f5 == 1 and wt5 == 2]
-                        if vals:
-                            feats[key] = vals[0]
+            yield key, value
+
+
+def parse_example(record: bytes) -> dict:
+    """{'image': bytes, 'shape': int32[3], 'ground_truth': float32[G, 5]}; map entries in any order, unknown features ignored"""
+    feats = {}
+    for key, value in _example_features(record):
+        if key in ('image', 'shape', 'ground_truth') and value is not None:
+            for f4, wt4, blist in _pb_parse(value):
+                if f4 == 1 and wt4 == 2:                      # bytes_list
+                    vals = [v for f5, wt5, v in _pb_parse(blist) if f5 == 1 and wt5 == 2]
+                    if vals:
+                        feats[key] = vals[0]
     missing = [k for k in ('image', 'shape', 'ground_truth') if k not in feats]
     if missing:
         raise ValueError(f'Example without the bytes_list feature(s) {missing}')
@@ -334,8 +343,15 @@ def _records(paths, verify):
             index += 1
 
 
-def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop):
-    """CPU work only (file reads, CRCs, protobuf, Huffman decoding): never a GPU call.  Puts (host batch, ground truths) or an exception."""
+def _voc_payload(examples):
+    return [torch.from_numpy(e['ground_truth']) for e in examples]
+
+
+def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop, parse=parse_example, extra=_voc_payload, refusal=None, skipped=None):
+    """CPU work only (file reads, CRCs, protobuf, Huffman decoding): never a GPU call.  Puts (host batch, extra(examples)) or an exception.
+    parse / extra: record -> example dict with an 'image', examples of a batch -> what travels with the pictures (VOC: the ground truths).
+    refusal (imagenet_data's on_unsupported='skip'): image bytes -> None, or the reason the decoder refuses the picture; such a record is left out before
+    batching -- the batch is filled from the records that follow -- and counted in skipped[0]."""
     def put(item):
         while not stop.is_set():
             try:
@@ -351,11 +367,21 @@ def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop):
             for index, payload in shuffle_stream(_records(paths, verify), buffer_size, rng):
                 if stop.is_set():
                     return
-                batch.append((index, payload))
+                if refusal is not None:
+                    try:
+                        example = parse(payload)
+                    except Exception as e:                             # noqa: BLE001
+                        raise ValueError(f'records {[index]}: {e}') from e
+                    if refusal(example['image']) is not None:
+                        skipped[0] += 1
+                        continue
+                    batch.append((index, example))
+                else:
+                    batch.append((index, payload))
                 if len(batch) < batch_size:
                     continue
                 try:
-                    examples = [parse_example(p) for _, p in batch]
+                    examples = [p if refusal is not None else parse(p) for _, p in batch]
                 except Exception as e:                                 # noqa: BLE001
                     raise ValueError(f'records {[i for i, _ in batch]}: {e}') from e
                 try:
@@ -364,7 +390,7 @@ def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop):
                     pic, _, msg = str(e).partition(': ')
                     k = int(pic.split()[1]) if pic.startswith('picture ') else 0
                     raise JpegError(f'record {batch[k][0]}: {msg}') from None
-                if not put((hb, [torch.from_numpy(e['ground_truth']) for e in examples])):
+                if not put((hb, extra(examples))):
                     return
                 batch, emitted = [], emitted + 1
             if emitted == 0:                                           # (drop_remainder with fewer records than a batch: nothing, for ever)
@@ -378,8 +404,10 @@ class _VOCIterator:
         self._decoder, self._augmentor = gen._decoder, gen._augmentor
         self._q = queue.Queue(maxsize=max(1, gen.prefetch))
         self._stop = threading.Event()
-        self._thread = threading.Thread(target=_worker, name='odtk-voc-loader', daemon=True,
-                                        args=(gen.tfrecords, gen.batch_size, gen.buffer_size, gen.seed, gen.verify, gen._decoder, self._q, self._stop))
+        self._thread = threading.Thread(target=_worker, name=gen.THREAD_NAME, daemon=True,
+                                        args=(gen.tfrecords, gen.batch_size, gen.buffer_size, gen.seed, gen.verify, gen._decoder, self._q, self._stop),
+                                        kwargs=gen._worker_options())
+        self._finish = gen._finish
         self._thread.start()
 
     def __iter__(self):
@@ -399,9 +427,9 @@ class _VOCIterator:
         if isinstance(item, BaseException):
             self.close()
             raise item
-        hb, gts = item
+        hb, extra = item
         images = self._decoder.reconstruct(hb)             # upload + odtk_jpeg_reconstruct, on the consumer's thread and current stream
-        return self._augmentor(images, gts)
+        return self._finish(images, extra)
 
     def close(self):
         self._stop.set()
@@ -418,6 +446,15 @@ class _VOCIterator:
 class VOCGenerator:
     """see get_generator"""
     endless = True                  # evaluate() asks for num_images (or num_val) before it reads a stream that never ends
+    THREAD_NAME = 'odtk-voc-loader'
+
+    def _worker_options(self):
+        """keyword arguments of _worker: the record layout of this generator (imagenet_data.ImageNetGenerator has its own)"""
+        return {}
+
+    def _finish(self, images, gts):
+        """the consumer's last stage: decoded pictures + what the worker sent with them -> one item of the stream"""
+        return self._augmentor(images, gts)
 
     def __init__(self, tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, decoder=None,
                  augmentor=None):

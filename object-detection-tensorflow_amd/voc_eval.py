@@ -247,7 +247,7 @@ class EvaluateMixin:
 
     def evaluate(self, num_images=None, generator=None, **kw):
         if getattr(self, 'is_pretraining', False):
-            raise ValueError("evaluate: a classification pre-training model has no detections")
+            raise ValueError("evaluate: a classification pre-training model has no detections (RetinaNet.evaluate measures its held-out accuracy)")
         if self.mode == 'test':
             return evaluate(self, generator, num_images, **kw)
         if generator is None:
