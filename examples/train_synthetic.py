@@ -78,6 +78,8 @@ for epoch in range(epochs):
     result = model.evaluate(batch_size=batch_size)
     mAP = 0.0 if np.isnan(result['mAP']) else result['mAP']
     print('>> val mAP (VOC07) %.4f over %d images, %d detections' % (mAP, 2 * batch_size, int(result['num_detections'].sum())))
+    coco = model.evaluate(batch_size=batch_size, metric='coco')      # IoU 0.50:0.95, >= on the threshold, at most 100 detections per image and class
+    print('>> val COCO AP %.4f  AP50 %.4f  AP75 %.4f' % tuple(0.0 if np.isnan(coco[k]) else coco[k] for k in ('AP', 'AP50', 'AP75')))
     model.save_weight('latest', os.path.join('/tmp', which, 'test'))
     if mAP > best_map:
         best_map = mAP

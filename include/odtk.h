@@ -697,6 +697,34 @@ int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, c
                   const int* gt_img, int num_gt, int num_images, int num_classes, float iou_thr, int metric, void* workspace,
                   unsigned char* tp_out, int* npos_out, double* ap_out, void* stream);
 
+/* COCO-style AP over the same inputs (same conventions, validity rules and limits as odtk_voc_eval): every (area range r, IoU threshold t) pair in one
+ * pass -- pycocotools' evaluateImg / accumulate without crowd regions, on this library's f32 IoU.  iou_thr [T] and area_rng [R][2] (lo, hi in px^2) are
+ * HOST arrays read during the call.  Limits: 1 <= T, 1 <= R, T * R <= 64, max_dets >= 1 (else ODTK_ERR_ARG and a message; nothing is launched).
+ *   IoU       exactly odtk_voc_eval's: f32, fmaxf / fminf, 0 unless the union is > 0.
+ *   Segments  per (image, class) the detections are ranked by descending score, ties to the lower sequence index; only the first max_dets take part,
+ *             the rest get code 2 for every (r, t); so does a detection that is not valid.
+ *   Ignore    for range r a GT row is IGNORED iff h * w < lo or h * w > hi (f32, both ends inclusive).  A segment's GT rows are visited with the
+ *             non-ignored ones first, then the ignored ones, each group in row order.
+ *   Matching  for threshold t, for each detection in rank order: best = thr[t], m = none; for each GT row in that order: skip it if it is already
+ *             matched at this (r, t); stop if m is a non-ignored row and this row is ignored; skip it if iou < best; otherwise best = iou, m = this row
+ *             (so >= on the threshold, and among equal IoUs the later row wins).  If m exists it becomes matched and the detection is a true positive
+ *             (1) if m is not ignored, else ignored (2).  Without m the detection is ignored (2) if its own area (y2 - y1) * (x2 - x1) is outside
+ *             [lo, hi], else a false positive (0).
+ *   npos      npos_out[r][c] = non-ignored GT rows of class c.
+ *   AP        per (r, t, c): the code-0 and code-1 detections of class c in global rank order (descending score, ties to the lower sequence index);
+ *             cumulative tp and fp along it; recall = tp / npos, precision = tp / (tp + fp + DBL_EPSILON); the precision envelope is the suffix
+ *             maximum; q_k = the envelope at the first position with recall >= x_k, x = linspace(0, 1, 101) in double (k / 100 as k * (1. / 100), x_100 = 1),
+ *             0 without such a position; ap_out = mean(q) in f64; recall_out = the last recall (0 without counted detections); both NaN where
+ *             npos_out[r][c] == 0.
+ * Outputs (device): match_out u8 [R][T][D] (0 false positive, 1 true positive, 2 ignored or dropped), npos_out [R][C], ap_out / recall_out f64 [R][T][C].
+ * Differs from the VOC matcher in three ways: >= instead of >, the best row that is NOT YET MATCHED instead of the best row, and the ignore rules.
+ * Deterministic: integer atomics only, reruns are bit-identical. */
+long long odtk_coco_eval_workspace_bytes(int num_det, int num_gt, int num_images, int num_classes, int num_thr, int num_areas);
+int odtk_coco_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                   const int* gt_img, int num_gt, int num_images, int num_classes, const float* iou_thr, int num_thr, const float* area_rng,
+                   int num_areas, int max_dets, void* workspace, unsigned char* match_out, int* npos_out, double* ap_out, double* recall_out,
+                   void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Classification metrics: held-out top-1 / top-k accuracy and cross-entropy over the logits of the pre-training head (csrc/classify.hip; no reference
  * counterpart).  logits: rows [N][ldl] f32, columns [C, ldl) are padding and never read; labels int32 [N].  Per row n with a label inside [0, C):

@@ -10,7 +10,7 @@ from . import _lib                      # noqa: F401
 from ._lib import BF16, F32, F32X3, OdtkError  # noqa: F401
 
 __all__ = ["BF16", "F32", "OdtkError", "SSD300", "YOLOv3", "RetinaNet", "FCOS", "CenterNet", "SSD512", "RefineDet320", "PFPNetR", "YOLOv2", "LHRCNN",
-           "VOCEvaluator", "evaluate", "get_generator", "dataset2tfrecord", "JpegBatchDecoder", "VOC_CLASSES", "ClassificationEvaluator",
+           "VOCEvaluator", "COCOEvaluator", "evaluate", "get_generator", "dataset2tfrecord", "JpegBatchDecoder", "VOC_CLASSES", "ClassificationEvaluator",
            "get_imagenet_generator", "imagenet_dataset2tfrecord"]
 
 
@@ -45,7 +45,7 @@ def __getattr__(name):
     if name == "LHRCNN":
         from .lhrcnn import LHRCNN
         return LHRCNN
-    if name in ("VOCEvaluator", "evaluate"):
+    if name in ("VOCEvaluator", "COCOEvaluator", "evaluate"):
         from . import voc_eval
         return getattr(voc_eval, name)
     if name in ("get_generator", "dataset2tfrecord", "xml_to_example", "JpegBatchDecoder", "VOC_CLASSES", "classname_to_ids"):

@@ -14,6 +14,14 @@
 //            the 11-point maxima or the precision envelope (suffix max) and the area sum (fixed-order tree reduction)
 // A radix pass is three launches: per-block digit histograms (+ digit totals by integer atomics), one workgroup per digit scanning its row of
 // block counts, and a stable scatter (wave ranks by 8 ballots, waves in order through LDS).
+//
+// COCO-style AP (odtk_coco_eval; semantics in include/odtk.h, restated by tests/coco_eval_ref.py) shares init and the three sorts and replaces the tail:
+//   gt prep  per sorted GT position: corners and h * w in f32 (the matcher reads them without the index indirection), npos[r][c] by integer atomics
+//   match    one wave per 64 positions of sort B; the segment heads among them (a ballot) are taken one after the other, lane = (area range r,
+//            IoU threshold t): box loads and the IoU are wave-uniform, the comparisons and the "matched" byte per (GT row, lane) are the lane's own
+//            -> no cross-lane traffic inside a segment and no atomics; match_out[r][t][i] = 0 / 1 / 2
+//   ap       one workgroup per (r, t, class): the backward chunk walk of voc_ap_kernel over the code-0 / code-1 positions; recall rises only at a
+//            TP position, which contributes envelope x #{k : previous recall < x_k <= this recall} of the 101 recall points
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -344,6 +352,204 @@ __global__ void __launch_bounds__(VE_THREADS) voc_ap_kernel(VocIn a, const int* 
     }
 }
 
+// ================================================================ COCO-style AP: every (area range, IoU threshold) pair in one pass
+constexpr int CE_MAX_PAIRS = 64;                          // lanes of a wave: R * T <= 64
+
+struct CocoPar {
+    float thr[CE_MAX_PAIRS], lo[CE_MAX_PAIRS], hi[CE_MAX_PAIRS];          // thr[t], [lo[r], hi[r]]
+    int T, R, max_dets;
+};
+
+// per sorted GT position m: corners (the expressions of voc_match_kernel) and the area h * w; npos[r][c] += 1 for every range that does not ignore the row
+__global__ void __launch_bounds__(VE_THREADS) coco_gt_prep_kernel(VocIn a, CocoPar cp, const int* gidx, float4* gbox, float* garea, int* npos) {
+    const int m = blockIdx.x * VE_THREADS + threadIdx.x;
+    if (m >= a.G) return;
+    const int j = gidx[m];
+    const float* r = a.gt + (size_t)j * 5;
+    const float yc = r[0], xc = r[1], h = r[2], w = r[3];
+    gbox[m] = make_float4(yc - h / 2.f, xc - w / 2.f, yc + h / 2.f, xc + w / 2.f);
+    const float ar = h * w;
+    garea[m] = ar;
+    const int c = gt_class(a, j);
+    if (c < 0) return;
+    for (int k = 0; k < cp.R; ++k)
+        if (!(ar < cp.lo[k] || ar > cp.hi[k])) atomicAdd(&npos[k * a.C + c], 1);
+}
+
+// wave w owns positions [64 w, 64 w + 64) of the (image, class)-segmented order: the lanes find the heads among them (and the heads' GT ranges) in
+// parallel, then the whole wave walks one head's segment at a time with lane = r * T + t.  matched: [G][R * T] bytes by sorted GT position, zeroed here
+// for the segment's rows (a GT row belongs to one segment, a segment to one wave).  match_out was filled with 2.
+__global__ void __launch_bounds__(VE_THREADS) coco_match_kernel(VocIn a, CocoPar cp, const int* order, const int* gidx, const float4* gbox,
+                                                                const float* garea, unsigned char* matched, unsigned char* match_out) {
+    const int lane = threadIdx.x & 63;
+    const int base = (blockIdx.x * (VE_THREADS / 64) + (threadIdx.x >> 6)) * 64;
+    const int p = base + lane;
+    bool head = false;
+    int g0 = 0, g1 = 0;
+    if (p < a.D) {
+        const int seg = det_segment(a, order[p]);
+        head = (p == 0 || det_segment(a, order[p - 1]) != seg) && seg % (a.C + 1) != a.C;
+        if (head) { g0 = gt_lower_bound(a, gidx, seg); g1 = gt_lower_bound(a, gidx, seg + 1); }
+    }
+    unsigned long long heads = __ballot(head);
+    const int RT = cp.R * cp.T;
+    const bool active = lane < RT;
+    const int r = active ? lane / cp.T : 0, t = active ? lane % cp.T : 0;
+    const float thr = cp.thr[t], lo = cp.lo[r], hi = cp.hi[r];
+    while (heads) {                                                         // wave-uniform
+        const int b = __ffsll((long long)heads) - 1;
+        heads &= heads - 1ull;
+        const int G0 = __shfl(g0, b), G1 = __shfl(g1, b);
+        const int p0 = base + b;
+        const int seg = det_segment(a, order[p0]);
+        if (active)
+            for (int m = G0; m < G1; ++m) matched[(size_t)m * RT + lane] = 0;
+        for (int q = p0, k = 0; q < a.D && k < cp.max_dets; ++q, ++k) {
+            const int i = order[q];
+            if (q > p0 && det_segment(a, i) != seg) break;
+            const float y1d = a.boxes[(size_t)i * 4 + 0], x1d = a.boxes[(size_t)i * 4 + 1];
+            const float y2d = a.boxes[(size_t)i * 4 + 2], x2d = a.boxes[(size_t)i * 4 + 3];
+            const float ad = (y2d - y1d) * (x2d - x1d);
+            // the two candidates of the visiting order "non-ignored rows, then ignored rows": the best untaken non-ignored row wins if there is one
+            float best_n = thr, best_i = thr;
+            int m_n = -1, m_i = -1;
+            for (int m = G0; m < G1; ++m) {
+                const float4 gb = gbox[m];
+                const float ag = garea[m];
+                const float ih = fmaxf(fminf(y2d, gb.z) - fmaxf(y1d, gb.x), 0.f);
+                const float iw = fmaxf(fminf(x2d, gb.w) - fmaxf(x1d, gb.y), 0.f);
+                const float inter = ih * iw;
+                const float uni = ad + (gb.z - gb.x) * (gb.w - gb.y) - inter;
+                const float iou = uni > 0.f ? inter / uni : 0.f;
+                if (!active || matched[(size_t)m * RT + lane]) continue;
+                if (ag < lo || ag > hi) {
+                    if (!(iou < best_i)) { best_i = iou; m_i = m; }
+                } else {
+                    if (!(iou < best_n)) { best_n = iou; m_n = m; }
+                }
+            }
+            if (!active) continue;
+            const int mm = m_n >= 0 ? m_n : m_i;
+            unsigned char code;
+            if (mm >= 0) {
+                matched[(size_t)mm * RT + lane] = 1;
+                code = m_n >= 0 ? 1 : 2;
+            } else {
+                code = (ad < lo || ad > hi) ? 2 : 0;
+            }
+            match_out[(size_t)lane * a.D + i] = code;
+        }
+    }
+}
+
+// a match code as a pair of counts: TP in the low word, FP in the high word (n <= 8 Mi: no carry between them); code 2 counts as neither
+__device__ __forceinline__ unsigned long long coco_packed(int code) { return code == 1 ? 1ull : (code == 0 ? (1ull << 32) : 0ull); }
+struct AddULL { __device__ unsigned long long operator()(unsigned long long x, unsigned long long y) const { return x + y; } };
+
+// x_k = np.linspace(0, 1, 101)[k] as numpy builds it: k * (1 / 100) in double, the last one exactly 1
+__device__ __forceinline__ double coco_recall_point(int k) { return k >= 100 ? 1.0 : (double)k * (1.0 / 100.0); }
+// #{k in [0, 101) : x_k <= n / dn}: a guess from the quotient, then settled by the comparisons themselves
+__device__ __forceinline__ int coco_points_upto(int n, double dn) {
+    const double rec = (double)n / dn;
+    int k = (int)(rec * 100.0) + 1;
+    k = k < 0 ? 0 : (k > 101 ? 101 : k);
+    while (k < 101 && rec >= coco_recall_point(k)) ++k;
+    while (k > 0 && !(rec >= coco_recall_point(k - 1))) --k;
+    return k;
+}
+
+// grid (C, R * T): AP and last recall of class c at pair (r, t) from the codes along the class's rank order (code 2 = not counted)
+__global__ void __launch_bounds__(VE_THREADS) coco_ap_kernel(VocIn a, int T, const int* order, const int* ndet, const int* npos,
+                                                             const unsigned char* match, double* ap_out, double* rec_out) {
+    __shared__ int shi[VE_THREADS];
+    __shared__ double shd[VE_THREADS];
+    __shared__ unsigned long long shl[VE_THREADS];
+    const int c = blockIdx.x, pair = blockIdx.y, t = threadIdx.x;
+    const size_t out = (size_t)pair * a.C + c;
+    int before = 0;
+    for (int k = t; k < c; k += VE_THREADS) before += ndet[k];
+    before = block_incl_scan(before, shi, AddI());
+    if (t == VE_THREADS - 1) shi[0] = before;
+    __syncthreads();
+    const int start = shi[0], n = ndet[c], np = npos[(pair / T) * a.C + c];
+    __syncthreads();
+    if (np == 0) {
+        if (t == 0) { ap_out[out] = __builtin_nan(""); rec_out[out] = __builtin_nan(""); }
+        return;
+    }
+    const unsigned char* code = match + (size_t)pair * a.D;
+    unsigned long long mine = 0;
+    for (int k = t; k < n; k += VE_THREADS) mine += coco_packed(code[order[start + k]]);
+    mine = block_incl_scan(mine, shl, AddULL());
+    if (t == VE_THREADS - 1) shl[0] = mine;
+    __syncthreads();
+    const unsigned long long total = shl[0];
+    __syncthreads();
+    const int total_tp = (int)(total & 0xffffffffull), total_fp = (int)(total >> 32);
+    const double dn = (double)np;
+    unsigned long long after_carry = 0;                                     // counted positions behind the current chunk
+    double env_carry = 0.0;                                                 // max precision behind the current chunk
+    double sum = 0.0;
+    const int CH = VE_THREADS * VE_AP_ITEMS;
+    for (int end = n; end > 0; end -= CH) {                                 // chunks from the back: [end - CH, end)
+        const int p0 = end - CH + t * VE_AP_ITEMS;
+        unsigned long long f[VE_AP_ITEMS];
+        unsigned long long cnt = 0;
+        for (int j = 0; j < VE_AP_ITEMS; ++j) {
+            const int k = p0 + j;
+            f[j] = (k >= 0 && k < end) ? coco_packed(code[order[start + k]]) : 0ull;
+            cnt += f[j];
+        }
+        const unsigned long long incl = block_incl_scan(cnt, shl, AddULL());
+        if (t == VE_THREADS - 1) shl[0] = incl;
+        __syncthreads();
+        const unsigned long long chunk = shl[0];
+        __syncthreads();
+        unsigned long long after = after_carry + chunk - incl;             // (each word of incl <= the same word of chunk: no borrow)
+        double prec[VE_AP_ITEMS];
+        int tpc[VE_AP_ITEMS];
+        double lmax = 0.0;
+        for (int j = VE_AP_ITEMS - 1; j >= 0; --j) {
+            tpc[j] = 0;
+            prec[j] = 0.0;
+            if (f[j]) {                                                     // a counted position: cumulative TP / FP up to and including it
+                tpc[j] = total_tp - (int)(after & 0xffffffffull);
+                const int fpc = total_fp - (int)(after >> 32);
+                prec[j] = (double)tpc[j] / ((double)(tpc[j] + fpc) + DBL_EPSILON);
+                if (prec[j] > lmax) lmax = prec[j];
+                after += f[j];
+            }
+        }
+        shd[VE_THREADS - 1 - t] = lmax;                                     // suffix max = prefix max over the reversed threads
+        __syncthreads();
+        double sv = shd[t];
+        __syncthreads();
+        sv = block_incl_scan(sv, shd, MaxD());
+        shd[VE_THREADS - 1 - t] = sv;                                       // shd[t] = max over threads >= t
+        __syncthreads();
+        double env = fmax(env_carry, t + 1 < VE_THREADS ? shd[t + 1] : 0.0);
+        const double chunk_max = shd[0];
+        __syncthreads();
+        for (int j = VE_AP_ITEMS - 1; j >= 0; --j) {
+            env = fmax(env, prec[j]);
+            if (f[j] == 1ull) sum += env * (double)(coco_points_upto(tpc[j], dn) - coco_points_upto(tpc[j] - 1, dn));
+        }
+        after_carry += chunk;
+        env_carry = fmax(env_carry, chunk_max);
+    }
+    shd[t] = sum;                                                           // fixed-order tree sum
+    __syncthreads();
+    for (int off = VE_THREADS / 2; off > 0; off >>= 1) {
+        if (t < off) shd[t] = shd[t] + shd[t + off];
+        __syncthreads();
+    }
+    if (t == 0) {
+        // x_0 = 0 is reached at the first counted position, whose envelope is the maximum of all precisions (0 without counted positions)
+        ap_out[out] = (shd[0] + env_carry) / 101.0;
+        rec_out[out] = (double)total_tp / dn;
+    }
+}
+
 int bits_for(long long maxval) {                                           // bits to represent 0..maxval
     int b = 0;
     while (b < 62 && (1ll << b) <= maxval) ++b;
@@ -377,6 +583,78 @@ bool voc_sizes_ok(int D, int G, int I, int C) {
 #define VOC_SIZES_MSG "voc_eval: num_det=%d num_gt=%d num_images=%d num_classes=%d outside the supported range (num_det <= %d, num_gt <= %d, " \
                       "1 <= num_images <= %d, 1 <= num_classes <= %d)"
 
+// init and the three sorts on `st`: what odtk_voc_eval and odtk_coco_eval share.  flags_out [D] is zeroed, npos [C] receives the GT rows per class.
+struct VocSorted {
+    int* rank;        // sort A: the per-class global rank order
+    int* seg;         // sort B: (image, class) segments, rank order inside each
+    const int* gt;    // sort G: GT indices by the (image, class) key
+    int* ndet;        // valid detections per class
+};
+int voc_sort(const VocIn& a, const VocLayout& L, char* ws, unsigned char* flags_out, int* npos, hipStream_t st, VocSorted* out) {
+    const int D = a.D, G = a.G, I = a.I, C = a.C;
+    int* idx[3] = {(int*)(ws + L.idx[0]), (int*)(ws + L.idx[1]), (int*)(ws + L.idx[2])};
+    int* gidx[2] = {(int*)(ws + L.gidx[0]), (int*)(ws + L.gidx[1])};
+    unsigned char* taken = (unsigned char*)(ws + L.taken);
+    unsigned* hist = (unsigned*)(ws + L.hist);
+    unsigned* tot = (unsigned*)(ws + L.tot);
+    int* ndet = (int*)(ws + L.ndet);
+    if (int e = zero_async(tot, L.ndet + (size_t)(C + 1) * 4 - L.tot, st)) return e;          // tot .. ndet
+    if (int e = zero_async(npos, (size_t)C * 4, st)) return e;
+    const int nmax = D > G ? D : G;
+    if (nmax > 0)
+        hipLaunchKernelGGL(voc_init_kernel, dim3((nmax + VE_TILE - 1) / VE_TILE), dim3(VE_THREADS), 0, st, a, flags_out, idx[0], gidx[0], taken, ndet,
+                           npos);
+    // a stable LSD radix sort of an index list, 8 bits per pass: the first pass reads `src` and writes `a0`, the later ones alternate a0 -> a1 -> a0;
+    // returns the buffer that holds the result.  Passes: score 4 + class <= 2 + image <= 3 + GT <= 4 = 13 <= VE_MAX_PASSES digit-total rows
+    int pass = 0;
+    auto radix = [&](int mode, int nbits, int n, int* src, int* a0, int* a1) -> int* {
+        if (n == 0) return src;
+        const int nb = (n + VE_TILE - 1) / VE_TILE;
+        int* cur = src;
+        for (int shift = 0; shift < nbits; shift += 8, ++pass) {
+            int* dst = cur == a0 ? a1 : a0;
+            unsigned* tp = tot + (size_t)256 * pass;
+            hipLaunchKernelGGL(voc_radix_hist_kernel, dim3(nb), dim3(VE_THREADS), 0, st, a, mode, shift, cur, n, nb, hist, tp);
+            hipLaunchKernelGGL(voc_radix_scan_kernel, dim3(256), dim3(VE_THREADS), 0, st, hist, nb, tp);
+            hipLaunchKernelGGL(voc_radix_scatter_kernel, dim3(nb), dim3(VE_THREADS), 0, st, a, mode, shift, cur, dst, n, nb, hist);
+            cur = dst;
+        }
+        return cur;
+    };
+    // sort A (per-class rank order): score bits first, then the class key [0, C]
+    int* p1 = radix(KEY_SCORE, 32, D, idx[0], idx[1], idx[0]);
+    p1 = radix(KEY_CLASS, bits_for(C), D, p1, p1 == idx[0] ? idx[1] : idx[0], p1);
+    // sort B ((image, class) segments): the order of A by image, in the two buffers that do not hold A
+    int* fb[2];
+    for (int k = 0, m = 0; k < 3; ++k) if (idx[k] != p1) fb[m++] = idx[k];
+    out->rank = p1;
+    out->seg = radix(KEY_IMAGE, bits_for(I - 1), D, p1, fb[0], fb[1]);
+    // sort G: GT rows by the (image, class) key
+    out->gt = radix(KEY_GT, bits_for((long long)I * (C + 1) - 1), G, gidx[0], gidx[1], gidx[0]);
+    out->ndet = ndet;
+    return ODTK_OK;
+}
+
+// odtk_coco_eval's workspace: the VOC layout, then the GT rows by sorted position, the matched bytes and the scratch of the reused init kernel
+struct CocoLayout {
+    VocLayout v;
+    size_t gbox, garea, matched, flags, npos_all, total;
+};
+CocoLayout coco_layout(int D, int G, int C, int RT) {
+    CocoLayout L;
+    L.v = voc_layout(D, G, C);
+    size_t off = L.v.total;
+    L.gbox = off; off += align256((size_t)G * 16);
+    L.garea = off; off += align256((size_t)G * 4);
+    L.matched = off; off += align256((size_t)G * RT);
+    L.flags = off; off += align256((size_t)D);
+    L.npos_all = off; off += align256((size_t)C * 4);
+    L.total = off;
+    return L;
+}
+bool coco_pairs_ok(int T, int R) { return T >= 1 && R >= 1 && (long long)T * R <= CE_MAX_PAIRS; }
+#define COCO_PAIRS_MSG "coco_eval: num_thr=%d num_areas=%d outside the supported range (1 <= num_thr, 1 <= num_areas, num_thr * num_areas <= %d)"
+
 }  // namespace
 }  // namespace odtk
 
@@ -401,53 +679,70 @@ extern "C" int odtk_voc_eval(const float* scores, const float* boxes, const int*
     ODTK_REQUIRE(num_gt == 0 || (gt_rows && gt_img), "voc_eval: null ground-truth pointer");
     const int D = num_det, G = num_gt, I = num_images, C = num_classes;
     const VocLayout L = voc_layout(D, G, C);
-    char* ws = (char*)workspace;
-    int* idx[3] = {(int*)(ws + L.idx[0]), (int*)(ws + L.idx[1]), (int*)(ws + L.idx[2])};
-    int* gidx[2] = {(int*)(ws + L.gidx[0]), (int*)(ws + L.gidx[1])};
-    unsigned char* taken = (unsigned char*)(ws + L.taken);
-    unsigned* hist = (unsigned*)(ws + L.hist);
-    unsigned* tot = (unsigned*)(ws + L.tot);
-    int* ndet = (int*)(ws + L.ndet);
     hipStream_t st = (hipStream_t)stream;
     VocIn a;
     a.scores = scores; a.boxes = boxes; a.det_cls = det_cls; a.det_img = det_img; a.gt = gt_rows; a.gt_img = gt_img;
     a.D = D; a.G = G; a.I = I; a.C = C;
-
-    if (int e = zero_async(tot, L.ndet + (size_t)(C + 1) * 4 - L.tot, st)) return e;          // tot .. ndet
-    if (int e = zero_async(npos_out, (size_t)C * 4, st)) return e;
-    const int nmax = D > G ? D : G;
-    if (nmax > 0)
-        hipLaunchKernelGGL(voc_init_kernel, dim3((nmax + VE_TILE - 1) / VE_TILE), dim3(VE_THREADS), 0, st, a, tp_out, idx[0], gidx[0], taken, ndet,
-                           npos_out);
-    // a stable LSD radix sort of an index list, 8 bits per pass: the first pass reads `src` and writes `a0`, the later ones alternate a0 -> a1 -> a0;
-    // returns the buffer that holds the result.  Passes: score 4 + class <= 2 + image <= 3 + GT <= 4 = 13 <= VE_MAX_PASSES digit-total rows
-    int pass = 0;
-    auto radix = [&](int mode, int nbits, int n, int* src, int* a0, int* a1) -> int* {
-        if (n == 0) return src;
-        const int nb = (n + VE_TILE - 1) / VE_TILE;
-        int* cur = src;
-        for (int shift = 0; shift < nbits; shift += 8, ++pass) {
-            int* dst = cur == a0 ? a1 : a0;
-            unsigned* tp = tot + (size_t)256 * pass;
-            hipLaunchKernelGGL(voc_radix_hist_kernel, dim3(nb), dim3(VE_THREADS), 0, st, a, mode, shift, cur, n, nb, hist, tp);
-            hipLaunchKernelGGL(voc_radix_scan_kernel, dim3(256), dim3(VE_THREADS), 0, st, hist, nb, tp);
-            hipLaunchKernelGGL(voc_radix_scatter_kernel, dim3(nb), dim3(VE_THREADS), 0, st, a, mode, shift, cur, dst, n, nb, hist);
-            cur = dst;
-        }
-        return cur;
-    };
-    // sort A (per-class rank order): score bits first, then the class key [0, C]
-    int* p1 = radix(KEY_SCORE, 32, D, idx[0], idx[1], idx[0]);
-    p1 = radix(KEY_CLASS, bits_for(C), D, p1, p1 == idx[0] ? idx[1] : idx[0], p1);
-    // sort B ((image, class) segments): the order of A by image, in the two buffers that do not hold A
-    int* fb[2];
-    for (int k = 0, m = 0; k < 3; ++k) if (idx[k] != p1) fb[m++] = idx[k];
-    int* p2 = radix(KEY_IMAGE, bits_for(I - 1), D, p1, fb[0], fb[1]);
-    // sort G: GT rows by the (image, class) key
-    const int* g = radix(KEY_GT, bits_for((long long)I * (C + 1) - 1), G, gidx[0], gidx[1], gidx[0]);
+    VocSorted s;
+    if (int e = voc_sort(a, L, (char*)workspace, tp_out, npos_out, st, &s)) return e;
     if (D > 0)
-        hipLaunchKernelGGL(voc_match_kernel, dim3((D + VE_THREADS - 1) / VE_THREADS), dim3(VE_THREADS), 0, st, a, p2, g, taken, iou_thr, tp_out);
-    hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(VE_THREADS), 0, st, a, p1, ndet, npos_out, tp_out, metric, ap_out);
+        hipLaunchKernelGGL(voc_match_kernel, dim3((D + VE_THREADS - 1) / VE_THREADS), dim3(VE_THREADS), 0, st, a, s.seg, s.gt,
+                           (unsigned char*)workspace + L.taken, iou_thr, tp_out);
+    hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(VE_THREADS), 0, st, a, s.rank, s.ndet, npos_out, tp_out, metric, ap_out);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+
+extern "C" long long odtk_coco_eval_workspace_bytes(int num_det, int num_gt, int num_images, int num_classes, int num_thr, int num_areas) {
+    if (!voc_sizes_ok(num_det, num_gt, num_images, num_classes)) {
+        set_error(VOC_SIZES_MSG, num_det, num_gt, num_images, num_classes, VE_MAX_DET, VE_MAX_GT, VE_MAX_IMAGES, VE_MAX_CLASSES);
+        return -1;
+    }
+    if (!coco_pairs_ok(num_thr, num_areas)) {
+        set_error(COCO_PAIRS_MSG, num_thr, num_areas, CE_MAX_PAIRS);
+        return -1;
+    }
+    return (long long)coco_layout(num_det, num_gt, num_classes, num_thr * num_areas).total;
+}
+
+extern "C" int odtk_coco_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                              const int* gt_img, int num_gt, int num_images, int num_classes, const float* iou_thr, int num_thr,
+                              const float* area_rng, int num_areas, int max_dets, void* workspace, unsigned char* match_out, int* npos_out,
+                              double* ap_out, double* recall_out, void* stream) {
+    ODTK_REQUIRE(voc_sizes_ok(num_det, num_gt, num_images, num_classes), VOC_SIZES_MSG, num_det, num_gt, num_images, num_classes, VE_MAX_DET,
+                 VE_MAX_GT, VE_MAX_IMAGES, VE_MAX_CLASSES);
+    ODTK_REQUIRE(coco_pairs_ok(num_thr, num_areas), COCO_PAIRS_MSG, num_thr, num_areas, CE_MAX_PAIRS);
+    ODTK_REQUIRE(max_dets >= 1, "coco_eval: max_dets %d (must be >= 1)", max_dets);
+    ODTK_REQUIRE(iou_thr && area_rng && workspace && npos_out && ap_out && recall_out, "coco_eval: null pointer");
+    ODTK_REQUIRE(num_det == 0 || (scores && boxes && det_cls && det_img && match_out), "coco_eval: null detection pointer");
+    ODTK_REQUIRE(num_gt == 0 || (gt_rows && gt_img), "coco_eval: null ground-truth pointer");
+    const int D = num_det, G = num_gt, C = num_classes, T = num_thr, R = num_areas, RT = T * R;
+    const CocoLayout L = coco_layout(D, G, C, RT);
+    char* ws = (char*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    VocIn a;
+    a.scores = scores; a.boxes = boxes; a.det_cls = det_cls; a.det_img = det_img; a.gt = gt_rows; a.gt_img = gt_img;
+    a.D = D; a.G = G; a.I = num_images; a.C = C;
+    CocoPar cp;
+    for (int k = 0; k < CE_MAX_PAIRS; ++k) {
+        cp.thr[k] = k < T ? iou_thr[k] : 0.f;
+        cp.lo[k] = k < R ? area_rng[2 * k] : 0.f;
+        cp.hi[k] = k < R ? area_rng[2 * k + 1] : 0.f;
+    }
+    cp.T = T; cp.R = R; cp.max_dets = max_dets;
+    VocSorted s;
+    if (int e = voc_sort(a, L.v, ws, (unsigned char*)(ws + L.flags), (int*)(ws + L.npos_all), st, &s)) return e;
+    if (int e = zero_async(npos_out, (size_t)R * C * 4, st)) return e;
+    float4* gbox = (float4*)(ws + L.gbox);
+    float* garea = (float*)(ws + L.garea);
+    if (G > 0)
+        hipLaunchKernelGGL(coco_gt_prep_kernel, dim3((G + VE_THREADS - 1) / VE_THREADS), dim3(VE_THREADS), 0, st, a, cp, s.gt, gbox, garea, npos_out);
+    if (D > 0) {
+        ODTK_CHECK_HIP(hipMemsetAsync(match_out, 2, (size_t)RT * D, st));   // beyond max_dets, invalid: never visited by the matcher
+        hipLaunchKernelGGL(coco_match_kernel, dim3((D + VE_THREADS - 1) / VE_THREADS), dim3(VE_THREADS), 0, st, a, cp, s.seg, s.gt, gbox, garea,
+                           (unsigned char*)(ws + L.matched), match_out);
+    }
+    hipLaunchKernelGGL(coco_ap_kernel, dim3(C, RT), dim3(VE_THREADS), 0, st, a, T, s.rank, s.ndet, npos_out, match_out, ap_out, recall_out);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }

@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import math
 
+import numpy as np
+
 import torch
 
 from . import _lib
@@ -765,6 +767,26 @@ def voc_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_c
     e = lambda t: _p(t) if t.numel() else None      # noqa: E731 -- an empty side passes NULL
     call("odtk_voc_eval", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), G, int(num_images), int(num_classes),
          float(iou_thr), VOC_METRICS[metric], _p(ws), e(tp), _p(npos), _p(ap), _stream())
+
+
+# ---------------------------------------------------------------- evaluation: COCO-style AP (csrc/voc_eval.hip, odtk_coco_eval)
+def coco_eval_workspace(D, G, I, C, T, R, device):
+    n = int(_lib.load().odtk_coco_eval_workspace_bytes(D, G, I, C, T, R))
+    if n < 0:
+        raise _lib.OdtkError(f"libodtk error: {_lib.load().odtk_last_error().decode()}")
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+
+
+def coco_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_classes, iou_thr, area_rng, max_dets, ws, match, npos, ap, recall):
+    """the inputs of voc_eval; iou_thr f32[T] and area_rng f32[R, 2] are HOST numpy arrays -> match u8[R, T, D], npos i32[R, C], ap / recall f64[R, T, C]
+    (include/odtk.h)"""
+    D, G = scores.shape[0], gt_rows.shape[0]
+    thr = np.ascontiguousarray(iou_thr, np.float32).reshape(-1)
+    rng = np.ascontiguousarray(area_rng, np.float32).reshape(-1, 2)
+    e = lambda t: _p(t) if t.numel() else None      # noqa: E731 -- an empty side passes NULL
+    call("odtk_coco_eval", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), G, int(num_images), int(num_classes),
+         C.c_void_p(thr.ctypes.data), thr.shape[0], C.c_void_p(rng.ctypes.data), rng.shape[0], int(max_dets), _p(ws), e(match), _p(npos), _p(ap),
+         _p(recall), _stream())
 
 
 # ---------------------------------------------------------------- evaluation: classification metrics (csrc/classify.hip)

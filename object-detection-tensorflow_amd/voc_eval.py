@@ -21,21 +21,13 @@ def _host(x):
     return np.asarray(x)
 
 
-class VOCEvaluator:
-    """add(detections, ground_truth) per image, result() once.  detections = [scores f32[K], bbox f32[K, 4] (y1, x1, y2, x2 px), class_id i32[K]]
-    (what every class's test_one_image returns; numpy or torch, host or device), ground_truth = f32[pad, 5] rows (yc, xc, h, w, cls px; cls < 0 =
-    padding).  Input errors raise ValueError; library errors OdtkError."""
+class _StagedEvaluator:
+    """what VOCEvaluator and COCOEvaluator share: the per-image staging on the host, the checked flat arrays and the one upload"""
 
-    def __init__(self, num_classes, iou_threshold=0.5, metric='voc07', device=None):
-        if metric not in METRICS:
-            raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+    def _init_common(self, num_classes, device):
         if not 1 <= int(num_classes) <= 1024:
             raise ValueError(f"num_classes must be in [1, 1024], not {num_classes}")
-        if not 0.0 <= float(iou_threshold) < 1.0:
-            raise ValueError(f"iou_threshold must be in [0, 1), not {iou_threshold}")
         self.num_classes = int(num_classes)
-        self.iou_threshold = float(iou_threshold)
-        self.metric = metric
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         self.device = torch.device(device)
@@ -94,27 +86,122 @@ class VOCEvaluator:
             raise ValueError(f"ground_truth of image {int(gi[np.argmax(bad)])}: class {int(gt[np.argmax(bad), 4])} >= num_classes {C}")
         return scores, boxes, cls.astype(np.int32), img, np.ascontiguousarray(gt), gi
 
-    def result(self):
-        """one upload, one odtk_voc_eval -> {'mAP', 'AP' f64[C] (NaN: no GT), 'npos', 'num_detections', 'tp' u8[D] in sequence order}"""
+    def _upload(self):
+        """_pack() as one host buffer of 4-byte words (scores | boxes | det_cls | det_img | gt_rows | gt_img), uploaded once -> the six device views in
+        the argument order of odtk_voc_eval / odtk_coco_eval, and the host class ids"""
         scores, boxes, cls, img, gt, gi = self._pack()
-        D, G, C = scores.shape[0], gt.shape[0], self.num_classes
-        I = max(self.num_images, 1)
-        # one host buffer of 4-byte words: scores | boxes | det_cls | det_img | gt_rows | gt_img
+        D, G = scores.shape[0], gt.shape[0]
         parts = [scores.view(np.int32), boxes.reshape(-1).view(np.int32), cls, img, gt.reshape(-1).view(np.int32), gi]
         host = torch.from_numpy(np.concatenate([np.ascontiguousarray(p, np.int32).reshape(-1) for p in parts]) if D + G else np.zeros(1, np.int32))
         dev = host.to(self.device)
         offs = np.cumsum([0] + [p.size for p in parts])
         seg = [dev[offs[k]: offs[k + 1]] for k in range(len(parts))]
+        return (seg[0].view(torch.float32), seg[1].view(torch.float32).view(-1, 4), seg[2], seg[3], seg[4].view(torch.float32).view(-1, 5),
+                seg[5]), cls
+
+
+class VOCEvaluator(_StagedEvaluator):
+    """add(detections, ground_truth) per image, result() once.  detections = [scores f32[K], bbox f32[K, 4] (y1, x1, y2, x2 px), class_id i32[K]]
+    (what every class's test_one_image returns; numpy or torch, host or device), ground_truth = f32[pad, 5] rows (yc, xc, h, w, cls px; cls < 0 =
+    padding).  Input errors raise ValueError; library errors OdtkError."""
+
+    def __init__(self, num_classes, iou_threshold=0.5, metric='voc07', device=None):
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+        if not 1 <= int(num_classes) <= 1024:
+            raise ValueError(f"num_classes must be in [1, 1024], not {num_classes}")
+        if not 0.0 <= float(iou_threshold) < 1.0:
+            raise ValueError(f"iou_threshold must be in [0, 1), not {iou_threshold}")
+        self.iou_threshold = float(iou_threshold)
+        self.metric = metric
+        self._init_common(num_classes, device)
+
+    def result(self):
+        """one upload, one odtk_voc_eval -> {'mAP', 'AP' f64[C] (NaN: no GT), 'npos', 'num_detections', 'tp' u8[D] in sequence order}"""
+        dev, cls = self._upload()
+        D, G, C = dev[0].shape[0], dev[4].shape[0], self.num_classes
+        I = max(self.num_images, 1)
         ws = ops.voc_eval_workspace(D, G, I, C, self.device)
         tp = torch.empty(D, dtype=torch.uint8, device=self.device)
         npos = torch.empty(C, dtype=torch.int32, device=self.device)
         ap = torch.empty(C, dtype=torch.float64, device=self.device)
-        ops.voc_eval(seg[0].view(torch.float32), seg[1].view(torch.float32).view(-1, 4), seg[2], seg[3], seg[4].view(torch.float32).view(-1, 5),
-                     seg[5], I, C, self.iou_threshold, self.metric, ws, tp, npos, ap)
+        ops.voc_eval(*dev, I, C, self.iou_threshold, self.metric, ws, tp, npos, ap)
         ap_h = ap.cpu().numpy()
         valid = ~np.isnan(ap_h)
         return {'mAP': float(ap_h[valid].mean()) if valid.any() else float('nan'), 'AP': ap_h, 'npos': npos.cpu().numpy().astype(np.int64),
                 'num_detections': np.bincount(cls, minlength=C).astype(np.int64), 'tp': tp.cpu().numpy()}
+
+
+COCO_IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10).astype(np.float32)
+COCO_AREA_RANGES = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], np.float32)       # all, small, medium, large (px^2)
+
+
+def _nanmean(x):
+    x = np.asarray(x, np.float64).reshape(-1)
+    ok = ~np.isnan(x)
+    return float(x[ok].mean()) if ok.any() else float('nan')
+
+
+class COCOEvaluator(_StagedEvaluator):
+    """COCO-style AP (include/odtk.h, odtk_coco_eval): add() / result() / reset() / num_images as VOCEvaluator.  iou_thresholds: ascending, distinct,
+    inside [0, 1) (default 0.50:0.05:0.95); area_ranges [R, 2] (lo, hi in px^2; default all, small < 32^2, medium, large > 96^2), area range 0 is the one
+    the summary numbers 'AP', 'AP50', 'AP75', 'AR' are taken at; max_dets: detections that count per (image, class), by descending score;
+    len(iou_thresholds) * len(area_ranges) <= 64.  Against the VOC matcher: IoU >= threshold (not >), a detection takes the best row that is NOT yet
+    matched (not "the best row, if it is free"), and rows / detections outside the area range are ignored rather than counted."""
+
+    def __init__(self, num_classes, iou_thresholds=None, area_ranges=None, max_dets=100, device=None):
+        thr = COCO_IOU_THRESHOLDS if iou_thresholds is None else np.asarray(iou_thresholds, np.float32).reshape(-1)
+        rng = COCO_AREA_RANGES if area_ranges is None else np.asarray(area_ranges, np.float32)
+        if thr.size < 1 or not np.all((thr >= 0) & (thr < 1)):
+            raise ValueError(f"iou_thresholds must be a non-empty list of values in [0, 1), not {thr.tolist()}")
+        if np.any(np.diff(thr) <= 0):
+            raise ValueError(f"iou_thresholds must be ascending without duplicates, not {thr.tolist()}")
+        if rng.ndim != 2 or rng.shape[1] != 2 or rng.shape[0] < 1 or np.any(np.isnan(rng)):
+            raise ValueError(f"area_ranges must be [R, 2] rows (lo, hi), R >= 1, not shape {tuple(rng.shape)}")
+        if np.any(rng[:, 0] > rng[:, 1]):
+            raise ValueError(f"area_ranges: lo > hi in {rng.tolist()}")
+        if thr.size * rng.shape[0] > 64:
+            raise ValueError(f"len(iou_thresholds) * len(area_ranges) = {thr.size} * {rng.shape[0]} exceeds 64")
+        if isinstance(max_dets, bool) or int(max_dets) != max_dets or int(max_dets) < 1:
+            raise ValueError(f"max_dets must be an integer >= 1, not {max_dets!r}")
+        self.iou_thresholds = np.ascontiguousarray(thr)
+        self.area_ranges = np.ascontiguousarray(rng)
+        self.max_dets = int(max_dets)
+        self._init_common(num_classes, device)
+
+    def result(self):
+        """one upload, one odtk_coco_eval, one read-back -> {'AP', 'AP50', 'AP75', 'APs', 'APm', 'APl', 'AR', 'AP_per_class' f64[C], 'ap' / 'recall' f64[R, T, C]
+        (NaN: no GT), 'npos' [R, C], 'match' u8[R, T, D] in sequence order (0 FP, 1 TP, 2 ignored or dropped), 'num_detections', 'iou_thresholds',
+        'area_ranges'}"""
+        dev, cls = self._upload()
+        D, G, C = dev[0].shape[0], dev[4].shape[0], self.num_classes
+        T, R = self.iou_thresholds.shape[0], self.area_ranges.shape[0]
+        I = max(self.num_images, 1)
+        ws = ops.coco_eval_workspace(D, G, I, C, T, R, self.device)
+        # one output buffer, one read-back: ap | recall (f64) | npos (i32) | match (u8)
+        n_ap, n_pos = R * T * C * 8, R * C * 4
+        out = torch.empty(2 * n_ap + n_pos + R * T * D, dtype=torch.uint8, device=self.device)
+        ap = out[:n_ap].view(torch.float64).view(R, T, C)
+        rec = out[n_ap: 2 * n_ap].view(torch.float64).view(R, T, C)
+        npos = out[2 * n_ap: 2 * n_ap + n_pos].view(torch.int32).view(R, C)
+        match = out[2 * n_ap + n_pos:].view(R, T, D)
+        ops.coco_eval(*dev, I, C, self.iou_thresholds, self.area_ranges, self.max_dets, ws, match, npos, ap, rec)
+        host = out.cpu().numpy()
+        ap_h = host[:n_ap].view(np.float64).reshape(R, T, C)
+        rec_h = host[n_ap: 2 * n_ap].view(np.float64).reshape(R, T, C)
+        npos_h = host[2 * n_ap: 2 * n_ap + n_pos].view(np.int32).reshape(R, C).astype(np.int64)
+        match_h = host[2 * n_ap + n_pos:].reshape(R, T, D)
+
+        def at(value, r=0):
+            k = np.nonzero(np.abs(self.iou_thresholds - np.float32(value)) < 1e-6)[0]
+            return _nanmean(ap_h[r, k[0]]) if k.size else float('nan')
+        four = R >= 4
+        return {'AP': _nanmean(ap_h[0]), 'AP50': at(0.5), 'AP75': at(0.75),
+                'APs': _nanmean(ap_h[1]) if four else float('nan'), 'APm': _nanmean(ap_h[2]) if four else float('nan'),
+                'APl': _nanmean(ap_h[3]) if four else float('nan'), 'AR': _nanmean(rec_h[0]),
+                'AP_per_class': np.array([_nanmean(ap_h[0, :, c]) for c in range(C)]), 'ap': ap_h, 'recall': rec_h, 'npos': npos_h, 'match': match_h,
+                'num_detections': np.bincount(cls, minlength=C).astype(np.int64), 'iou_thresholds': self.iou_thresholds.copy(),
+                'area_ranges': self.area_ranges.copy()}
 
 
 def _batches(generator):
@@ -158,12 +245,15 @@ def _chunks(generator, batch_size, num_images):
         yield flush(have)
 
 
-def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='voc07', batch_size=1):
+def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='voc07', batch_size=1, max_dets=100):
     """VOC mAP of `model` (test mode) over `generator`: batches (images [B, H, W, 3] or channels_first, ground_truth [B, pad, 5]) -- the
     train_generator contract -- or an (initializer, iterator) pair.  batch_size 1 (default): each batch is split into single images for
     model.test_one_image.  batch_size B > 1: the batches are regrouped into chunks of B images for model.test_images (the model must have been built with
     test_batch_size >= B, or be one of the classes whose test_images is the documented loop).  Stops after `num_images` images or at the end of one pass.
-    Defaults: the model's val_generator and num_val (when > 0)."""
+    Defaults: the model's val_generator and num_val (when > 0).  metric 'coco': the COCO-style protocol (COCOEvaluator with its default thresholds and
+    area ranges, `max_dets` detections per image and class; `iou_threshold` has no meaning there and must stay at its default)."""
+    if metric == 'coco' and iou_threshold != 0.5:
+        raise ValueError("evaluate: metric='coco' averages over its own IoU thresholds; iou_threshold must be left at its default")
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"evaluate: batch_size must be >= 1, not {batch_size}")
@@ -181,7 +271,11 @@ def evaluate(model, generator=None, num_images=None, iou_threshold=0.5, metric='
     if num_images is None and getattr(generator, 'endless', False):
         raise ValueError("evaluate: this generator repeats without end (voc_data.get_generator): give num_images, or num_val > 0 in the data provider")
     dev = getattr(model, 'dev', None)
-    ev = VOCEvaluator(model.config['num_classes'], iou_threshold, metric, device=dev if dev is not None and dev.type == 'cuda' else None)
+    dev = dev if dev is not None and dev.type == 'cuda' else None
+    if metric == 'coco':
+        ev = COCOEvaluator(model.config['num_classes'], max_dets=max_dets, device=dev)
+    else:
+        ev = VOCEvaluator(model.config['num_classes'], iou_threshold, metric, device=dev)
     if batch_size > 1:
         for images, gt in _chunks(generator, batch_size, num_images):
             for det, g in zip(model.test_images(images), gt):

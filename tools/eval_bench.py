@@ -5,6 +5,9 @@
   * per input: result() with device synchronisation (host packing, the one upload, the kernels, the read-back), the kernels alone (odtk_voc_eval
     on uploaded tensors, HIP events) and the NumPy restatement (tests/voc_eval_ref.evaluate_fast) on 16 threads;
   * SSD300.evaluate on the exact f32 engine (test mode, score threshold 0.01) in images/s, and the evaluator's share of it.
+  * --coco: only the COCO-style leg on the VOC07-test sized input (odtk.COCOEvaluator, default 10 thresholds x 4 area ranges, max_dets 100): result()
+    wall time, the kernels alone (odtk_coco_eval, HIP events), ten VOCEvaluator.result() calls at the ten thresholds on the same data (what the
+    ten-threshold number cost before odtk_coco_eval existed) and the NumPy restatement (tests/coco_eval_ref.evaluate_fast).
 Per-kernel times: run `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/eval_bench.py --kernels-only` separately."""
 import argparse
 import json
@@ -21,6 +24,7 @@ import torch            # noqa: E402
 import odtk             # noqa: E402
 from odtk import ops    # noqa: E402
 import voc_eval_ref as R                # noqa: E402
+import coco_eval_ref as CR              # noqa: E402
 
 
 def synthetic(seed, n_img, C, det_per_img, gt_mean, one_class=None):
@@ -79,6 +83,55 @@ def time_kernels(ev, C, dev, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def coco_leg(dev, reps):
+    C = 20
+    dets, gts = synthetic(0, 4952, C, 100, 2.4, None)
+    ev = odtk.COCOEvaluator(C, device=dev)
+    voc = [odtk.VOCEvaluator(C, float(t), 'area', device=dev) for t in ev.iou_thresholds]
+    for d, g in zip(dets, gts):
+        ev.add(list(d), g)
+        for v in voc:
+            v.add(list(d), g)
+
+    def wall(f):
+        f()
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t)
+        return 1e3 * float(np.median(ts))
+    r = ev.result()
+    row = {'images': len(gts), 'detections': int(r['num_detections'].sum()), 'gt_rows': sum(len(g) for g in gts), 'pairs': int(r['ap'].shape[0] * r['ap'].shape[1]),
+           'AP': r['AP'], 'AP50': r['AP50'], 'AP75': r['AP75'], 'result_ms': wall(ev.result), 'ten_voc_results_ms': wall(lambda: [v.result() for v in voc])}
+    args, _ = ev._upload()
+    D, G, I = args[0].shape[0], args[4].shape[0], ev.num_images
+    T, Rn = ev.iou_thresholds.shape[0], ev.area_ranges.shape[0]
+    ws = ops.coco_eval_workspace(D, G, I, C, T, Rn, dev)
+    match = torch.empty(Rn, T, D, dtype=torch.uint8, device=dev)
+    npos = torch.empty(Rn, C, dtype=torch.int32, device=dev)
+    ap, rec = (torch.empty(Rn, T, C, dtype=torch.float64, device=dev) for _ in range(2))
+    run = lambda: ops.coco_eval(*args, I, C, ev.iou_thresholds, ev.area_ranges, ev.max_dets, ws, match, npos, ap, rec)   # noqa: E731
+    run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    row['kernels_ms'] = e0.elapsed_time(e1) / reps
+    row['voc_kernels_ms'] = time_kernels(voc[0], C, dev, reps)
+    t = time.perf_counter()
+    ref = CR.evaluate_fast(dets, gts, C)
+    row['numpy_ref_ms'] = 1e3 * (time.perf_counter() - t)
+    row['match_equal_ref'] = bool(np.array_equal(ref['match'], r['match']))
+    row['ap_max_abs_diff_ref'] = float(np.nanmax(np.abs(ref['ap'] - r['ap'])))
+    return row
+
+
 def time_numpy(dets, gts, C):
     t = time.perf_counter()
     R.evaluate_fast(dets, gts, C)
@@ -125,10 +178,14 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--e2e-images', type=int, default=256)
     ap.add_argument('--kernels-only', action='store_true', help='a few kernel runs of both inputs (for rocprofv3 --kernel-trace --stats)')
+    ap.add_argument('--coco', action='store_true', help='only the COCO-style leg (odtk.COCOEvaluator against ten VOC passes and the NumPy restatement)')
     a = ap.parse_args()
     torch.set_num_threads(16)
     os.environ.setdefault('OMP_NUM_THREADS', '16')
     dev = torch.device('cuda:0')
+    if a.coco:
+        print(json.dumps({'coco_voc07': coco_leg(dev, a.reps)}))
+        return
     out = {}
     for name, spec in [('voc07', (0, 4952, 20, 100, 2.4, None)), ('stress_2m', (1, 100000, 20, 20, 2, 0))]:
         t0 = time.perf_counter()
