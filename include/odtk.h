@@ -696,9 +696,27 @@ long long odtk_voc_eval_workspace_bytes(int num_det, int num_gt, int num_images,
 int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
                   const int* gt_img, int num_gt, int num_images, int num_classes, float iou_thr, int metric, void* workspace,
                   unsigned char* tp_out, int* npos_out, double* ap_out, void* stream);
+/* odtk_voc_eval with a flag per ground-truth row: gt_flags [G] bytes on the device, 0 = an ordinary object, 1 = ignore (PASCAL VOC `difficult`),
+ * 2 = crowd (here the same as 1); NULL = every row 0, and then every output is bit-identical to odtk_voc_eval's (which is this call with NULL).
+ * The devkit's VOCevaldet:
+ *   Ranking, IoU   unchanged.
+ *   Matching       each detection, in rank order, takes the first GT row of its (image, class) with the largest IoU over ALL rows, flagged or not.
+ *                  If that IoU > iou_thr and the row's flag is non-zero: match_out[i] = 2, and the row is NOT marked taken (a flagged row absorbs any
+ *                  number of detections).  If that IoU > iou_thr, the flag is 0 and the row is free: 1, and the row becomes taken.  Otherwise 0.
+ *   Counts         npos_out[c] = the flag-0 rows of class c, nign_out[c] = the flagged ones (nign_out may be NULL).
+ *   AP             over the code-0 and code-1 detections only, in the same rank order: a code-2 detection adds to neither the cumulative TP nor the
+ *                  cumulative FP (precision = TP / counted detections so far).  Both metrics are otherwise odtk_voc_eval's, summation order included.
+ *                  NaN where npos_out[c] == 0, even if the class has flagged rows.
+ * A flag value above 2 fails with ODTK_ERR_ARG and the row index in odtk_last_error(); the outputs are then not valid.  The values are checked on
+ * the device, so WITH gt_flags the call waits for `stream` before it returns (it cannot be captured into a graph); with NULL it does not.
+ * Workspace: odtk_voc_eval_workspace_bytes suffices -- the flags are read in place (through the sorted row index) and the check uses a word of the
+ * workspace that no sort pass needs. */
+int odtk_voc_eval_flags(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                        const int* gt_img, const unsigned char* gt_flags, int num_gt, int num_images, int num_classes, float iou_thr, int metric,
+                        void* workspace, unsigned char* match_out, int* npos_out, int* nign_out, double* ap_out, void* stream);
 
 /* COCO-style AP over the same inputs (same conventions, validity rules and limits as odtk_voc_eval): every (area range r, IoU threshold t) pair in one
- * pass -- pycocotools' evaluateImg / accumulate without crowd regions, on this library's f32 IoU.  iou_thr [T] and area_rng [R][2] (lo, hi in px^2) are
+ * pass -- pycocotools' evaluateImg / accumulate on this library's f32 IoU (ignore and crowd rows: odtk_coco_eval_flags below).  iou_thr [T] and area_rng [R][2] (lo, hi in px^2) are
  * HOST arrays read during the call.  Limits: 1 <= T, 1 <= R, T * R <= 64, max_dets >= 1 (else ODTK_ERR_ARG and a message; nothing is launched).
  *   IoU       exactly odtk_voc_eval's: f32, fmaxf / fminf, 0 unless the union is > 0.
  *   Segments  per (image, class) the detections are ranked by descending score, ties to the lower sequence index; only the first max_dets take part,
@@ -724,6 +742,24 @@ int odtk_coco_eval(const float* scores, const float* boxes, const int* det_cls, 
                    const int* gt_img, int num_gt, int num_images, int num_classes, const float* iou_thr, int num_thr, const float* area_rng,
                    int num_areas, int max_dets, void* workspace, unsigned char* match_out, int* npos_out, double* ap_out, double* recall_out,
                    void* stream);
+/* odtk_coco_eval with a flag per ground-truth row (gt_flags [G] bytes on the device: 0 ordinary, 1 = pycocotools' `ignore` with iscrowd = 0, 2 =
+ * iscrowd = 1; NULL = every row 0, bit-identical to odtk_coco_eval, which is this call with NULL).  pycocotools' evaluateImg with crowd; against the
+ * text above only this changes:
+ *   Ignore    for range r a GT row is IGNORED iff its flag is non-zero OR h * w is outside [lo, hi].  The visiting order stays "non-ignored rows first,
+ *             then ignored ones, each group in row order".
+ *   Overlap   against a flag-2 row: intersection / det_area (f32; det_area = (y2 - y1) * (x2 - x1); 0 unless det_area > 0).  Against every other row:
+ *             the IoU above, bit for bit.
+ *   Matching  "skip a row already matched at this (r, t)" applies only to rows whose flag is not 2: a crowd row stays available after it is matched
+ *             and may absorb any number of detections (each gets code 2).  A flag-1 row is matched once, like an out-of-range row.  The stop rule,
+ *             >= on the threshold, the later row among equal overlaps, code 1 / 2 by the matched row being non-ignored / ignored, the unmatched
+ *             detection's own area, max_dets, npos (non-ignored rows), AP and recall are unchanged.
+ * A flag value above 2 fails with ODTK_ERR_ARG and the row index in odtk_last_error(); the outputs are then not valid.  As in odtk_voc_eval_flags the
+ * call waits for `stream` when gt_flags is given.  Workspace: odtk_coco_eval_workspace_bytes suffices (flags are read through the sorted row index).
+ * Deterministic: integer atomics only. */
+int odtk_coco_eval_flags(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                         const int* gt_img, const unsigned char* gt_flags, int num_gt, int num_images, int num_classes, const float* iou_thr,
+                         int num_thr, const float* area_rng, int num_areas, int max_dets, void* workspace, unsigned char* match_out, int* npos_out,
+                         double* ap_out, double* recall_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Classification metrics: held-out top-1 / top-k accuracy and cross-entropy over the logits of the pre-training head (csrc/classify.hip; no reference

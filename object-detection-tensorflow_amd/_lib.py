@@ -182,8 +182,10 @@ SIGNATURES = {
     "odtk_comm_destroy": (_i, [_vp]),
     "odtk_voc_eval_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "odtk_voc_eval": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_voc_eval_flags": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_coco_eval_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "odtk_coco_eval": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_coco_eval_flags": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_classify_eval": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_jpeg_info": (_i, [_vp, C.c_size_t, C.POINTER(JpegInfo)]),
     "odtk_jpeg_entropy_decode": (_i, [_vp, C.c_size_t, _vp, C.c_size_t, _vp]),

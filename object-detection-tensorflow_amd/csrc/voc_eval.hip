@@ -22,6 +22,12 @@
 //            -> no cross-lane traffic inside a segment and no atomics; match_out[r][t][i] = 0 / 1 / 2
 //   ap       one workgroup per (r, t, class): the backward chunk walk of voc_ap_kernel over the code-0 / code-1 positions; recall rises only at a
 //            TP position, which contributes envelope x #{k : previous recall < x_k <= this recall} of the 101 recall points
+//
+// Ground-truth flags (odtk_voc_eval_flags / odtk_coco_eval_flags; gt_flags [G] bytes, NULL = all 0): 0 ordinary, 1 ignore (VOC `difficult`), 2 crowd.
+// They are read in place, by GT row (init) or through the sorted GT index (gidx[m]: prep and the two matchers) -- no extra workspace.  init also checks
+// the values: the largest row index + 1 with a flag above 2 goes by an integer atomicMax into a spare digit-total row of the workspace, which the
+// entry point reads back (its only synchronisation, and only with gt_flags given) to refuse the call.  With gt_flags == NULL every kernel computes what
+// it computed before the flags existed, bit for bit.
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -40,7 +46,9 @@ struct VocIn {
     const float* scores; const float* boxes; const int* det_cls; const int* det_img;
     const float* gt; const int* gt_img;
     int D, G, I, C;
+    const unsigned char* gfl;                             // per GT row: 0 ordinary, 1 ignore, 2 crowd; NULL = all 0
 };
+__device__ __forceinline__ int gt_flag(const VocIn& a, int j) { return a.gfl ? (int)a.gfl[j] : 0; }
 
 __device__ __forceinline__ bool det_valid(const VocIn& a, int i) {
     const unsigned u = __float_as_uint(a.scores[i]);
@@ -80,10 +88,10 @@ __device__ __forceinline__ int radix_digit(const VocIn& a, int mode, int shift, 
 
 // ---------------------------------------------------------------- init: outputs, identity lists, per-class counts
 __global__ void __launch_bounds__(VE_THREADS) voc_init_kernel(VocIn a, unsigned char* tp_out, int* det_idx, int* gt_idx, unsigned char* taken,
-                                                              int* ndet, int* npos) {
-    __shared__ int hd[VE_MAX_CLASSES], hg[VE_MAX_CLASSES];
+                                                              int* ndet, int* npos, int* nign, int* bad) {
+    __shared__ int hd[VE_MAX_CLASSES], hg[VE_MAX_CLASSES], hf[VE_MAX_CLASSES];      // valid detections, flag-0 GT rows, flagged GT rows
     const int t = threadIdx.x;
-    for (int c = t; c < a.C; c += VE_THREADS) { hd[c] = 0; hg[c] = 0; }
+    for (int c = t; c < a.C; c += VE_THREADS) { hd[c] = 0; hg[c] = 0; hf[c] = 0; }
     __syncthreads();
     const int base = blockIdx.x * VE_TILE;
     for (int k = 0; k < VE_ITEMS; ++k) {
@@ -97,13 +105,16 @@ __global__ void __launch_bounds__(VE_THREADS) voc_init_kernel(VocIn a, unsigned 
             gt_idx[i] = i;
             taken[i] = 0;
             const int c = gt_class(a, i);
-            if (c >= 0) atomicAdd(&hg[c], 1);
+            const int f = gt_flag(a, i);
+            if (f > 2) atomicMax(bad, i + 1);                              // not a flag: the entry point refuses the call
+            if (c >= 0) atomicAdd(f ? &hf[c] : &hg[c], 1);
         }
     }
     __syncthreads();
     for (int c = t; c < a.C; c += VE_THREADS) {
         if (hd[c]) atomicAdd(&ndet[c], hd[c]);
         if (hg[c]) atomicAdd(&npos[c], hg[c]);
+        if (nign && hf[c]) atomicAdd(&nign[c], hf[c]);
     }
 }
 
@@ -138,6 +149,7 @@ __device__ __forceinline__ T block_incl_scan(T v, T* sh, Op op) {             //
 }
 struct AddU { __device__ unsigned operator()(unsigned x, unsigned y) const { return x + y; } };
 struct AddI { __device__ int operator()(int x, int y) const { return x + y; } };
+struct AddULL { __device__ unsigned long long operator()(unsigned long long x, unsigned long long y) const { return x + y; } };
 struct MaxD { __device__ double operator()(double x, double y) const { return x > y ? x : y; } };
 
 // one workgroup per digit d: exclusive scan of row d of hist, offset by the counts of all smaller digits
@@ -233,18 +245,27 @@ __global__ void __launch_bounds__(VE_THREADS) voc_match_kernel(VocIn a, const in
             const float iou = uni > 0.f ? inter / uni : 0.f;
             if (iou > best) { best = iou; bj = m; }
         }
-        if (bj >= 0 && best > iou_thr && !taken[bj]) {
-            taken[bj] = 1;
-            tp_out[i] = 1;
+        if (bj >= 0 && best > iou_thr) {
+            if (gt_flag(a, gidx[bj])) {
+                tp_out[i] = 2;                                              // on a flagged row: neither TP nor FP, and the row stays free
+            } else if (!taken[bj]) {
+                taken[bj] = 1;
+                tp_out[i] = 1;
+            }
         }
     }
 }
 
 // ---------------------------------------------------------------- AP per class
+// a VOC match code as a pair of counts: TP in the low word, counted positions (TP or FP) in the high word; code 2 (on a flagged row) counts as neither
+__device__ __forceinline__ unsigned long long voc_packed(int code) { return code == 1 ? ((1ull << 32) | 1ull) : (code == 0 ? (1ull << 32) : 0ull); }
+
+// along the class's rank order the code-2 positions are skipped: precision = cumulative TP / counted positions so far (= the position + 1 without code 2)
 __global__ void __launch_bounds__(VE_THREADS) voc_ap_kernel(VocIn a, const int* order, const int* ndet, const int* npos, const unsigned char* tp,
                                                             int metric, double* ap_out) {
     __shared__ int shi[VE_THREADS];
     __shared__ double shd[VE_THREADS];
+    __shared__ unsigned long long shl[VE_THREADS];
     __shared__ double pk_sh[11][VE_THREADS];
     const int c = blockIdx.x, t = threadIdx.x;
     int before = 0;
@@ -258,54 +279,54 @@ __global__ void __launch_bounds__(VE_THREADS) voc_ap_kernel(VocIn a, const int* 
         if (t == 0) ap_out[c] = __builtin_nan("");
         return;
     }
-    // total TP of the class
-    int mine = 0;
-    for (int k = t; k < n; k += VE_THREADS) mine += tp[order[start + k]];
-    mine = block_incl_scan(mine, shi, AddI());
-    if (t == VE_THREADS - 1) shi[0] = mine;
+    // total TP and counted positions of the class
+    unsigned long long mine = 0;
+    for (int k = t; k < n; k += VE_THREADS) mine += voc_packed(tp[order[start + k]]);
+    mine = block_incl_scan(mine, shl, AddULL());
+    if (t == VE_THREADS - 1) shl[0] = mine;
     __syncthreads();
-    const int total = shi[0];
+    const unsigned long long total = shl[0];
     __syncthreads();
+    const int total_tp = (int)(total & 0xffffffffull), total_cnt = (int)(total >> 32);
     const double dn = (double)np;
     double thr[11], pk[11];
     for (int k = 0; k < 11; ++k) { thr[k] = (double)k * 0.1; pk[k] = -1.0; }   // t_k = k * 0.1 in double: np.arange(0., 1.1, 0.1)
-    int after_carry = 0;                                                    // TP at rank positions behind the current chunk
+    unsigned long long after_carry = 0;                                     // TP / counted positions behind the current chunk
     double env_carry = 0.0;                                                 // max precision behind the current chunk (the sentinel 0 included)
     double area = 0.0;
     const int CH = VE_THREADS * VE_AP_ITEMS;
     for (int end = n; end > 0; end -= CH) {                                 // chunks from the back: [end - CH, end)
         const int s = end - CH;
         const int p0 = s + t * VE_AP_ITEMS;
-        int f[VE_AP_ITEMS];
-        int cnt = 0;
+        unsigned long long f[VE_AP_ITEMS];
+        unsigned long long cnt = 0;
         for (int j = 0; j < VE_AP_ITEMS; ++j) {
             const int k = p0 + j;
-            f[j] = (k >= 0 && k < end) ? tp[order[start + k]] : 0;
+            f[j] = (k >= 0 && k < end) ? voc_packed(tp[order[start + k]]) : 0ull;
             cnt += f[j];
         }
-        // TP behind this thread's items: a suffix scan = a prefix scan over reversed threads
-        const int incl = block_incl_scan(cnt, shi, AddI());                // (prefix over t; the suffix is chunk total - incl)
-        if (t == VE_THREADS - 1) shi[0] = incl;
+        // counts behind this thread's items: a suffix scan = a prefix scan over reversed threads
+        const unsigned long long incl = block_incl_scan(cnt, shl, AddULL());  // (prefix over t; the suffix is chunk total - incl)
+        if (t == VE_THREADS - 1) shl[0] = incl;
         __syncthreads();
-        const int chunk_tp = shi[0];
+        const unsigned long long chunk = shl[0];
         __syncthreads();
-        int after = after_carry + chunk_tp - incl;
+        unsigned long long after = after_carry + chunk - incl;             // (each word of incl <= the same word of chunk: no borrow)
         double prec[VE_AP_ITEMS];
         int tpc[VE_AP_ITEMS];
         double lmax = 0.0;
         for (int j = VE_AP_ITEMS - 1; j >= 0; --j) {
-            const int k = p0 + j;
-            if (k >= 0 && k < end) {
+            tpc[j] = 0;
+            prec[j] = 0.0;
+            if (f[j]) {                                                     // a counted position (inside the chunk, code 0 or 1)
                 after += f[j];
-                tpc[j] = total - after + f[j];                              // cumulative TP up to and including position k
-                prec[j] = (double)tpc[j] / fmax((double)(k + 1), DBL_EPSILON);
+                tpc[j] = total_tp - (int)(after & 0xffffffffull) + (int)(f[j] & 1ull);   // cumulative TP up to and including this position
+                const int upto = total_cnt - (int)(after >> 32) + 1;       // counted positions up to and including it
+                prec[j] = (double)tpc[j] / fmax((double)upto, DBL_EPSILON);
                 const double rec = (double)tpc[j] / dn;
                 if (prec[j] > lmax) lmax = prec[j];
                 for (int q = 0; q < 11; ++q)
                     if (rec >= thr[q] && prec[j] > pk[q]) pk[q] = prec[j];
-            } else {
-                tpc[j] = 0;
-                prec[j] = 0.0;
             }
         }
         // precision envelope: max over this thread's later items, the later threads of the chunk and the chunk behind
@@ -320,12 +341,10 @@ __global__ void __launch_bounds__(VE_THREADS) voc_ap_kernel(VocIn a, const int* 
         const double chunk_max = shd[0];
         __syncthreads();
         for (int j = VE_AP_ITEMS - 1; j >= 0; --j) {
-            const int k = p0 + j;
-            if (k < 0 || k >= end) continue;
             env = fmax(env, prec[j]);
-            if (f[j]) area += ((double)tpc[j] / dn - (double)(tpc[j] - 1) / dn) * env;
+            if (f[j] & 1ull) area += ((double)tpc[j] / dn - (double)(tpc[j] - 1) / dn) * env;
         }
-        after_carry += chunk_tp;
+        after_carry += chunk;
         env_carry = fmax(env_carry, chunk_max);
     }
     double r;
@@ -361,6 +380,7 @@ struct CocoPar {
 };
 
 // per sorted GT position m: corners (the expressions of voc_match_kernel) and the area h * w; npos[r][c] += 1 for every range that does not ignore the row
+// (a flagged row is ignored in every range)
 __global__ void __launch_bounds__(VE_THREADS) coco_gt_prep_kernel(VocIn a, CocoPar cp, const int* gidx, float4* gbox, float* garea, int* npos) {
     const int m = blockIdx.x * VE_THREADS + threadIdx.x;
     if (m >= a.G) return;
@@ -371,7 +391,7 @@ __global__ void __launch_bounds__(VE_THREADS) coco_gt_prep_kernel(VocIn a, CocoP
     const float ar = h * w;
     garea[m] = ar;
     const int c = gt_class(a, j);
-    if (c < 0) return;
+    if (c < 0 || gt_flag(a, j)) return;
     for (int k = 0; k < cp.R; ++k)
         if (!(ar < cp.lo[k] || ar > cp.hi[k])) atomicAdd(&npos[k * a.C + c], 1);
 }
@@ -379,6 +399,9 @@ __global__ void __launch_bounds__(VE_THREADS) coco_gt_prep_kernel(VocIn a, CocoP
 // wave w owns positions [64 w, 64 w + 64) of the (image, class)-segmented order: the lanes find the heads among them (and the heads' GT ranges) in
 // parallel, then the whole wave walks one head's segment at a time with lane = r * T + t.  matched: [G][R * T] bytes by sorted GT position, zeroed here
 // for the segment's rows (a GT row belongs to one segment, a segment to one wave).  match_out was filled with 2.
+// A row's flag is the same for every lane (m is wave-uniform): a flagged row is ignored in every range; a crowd row (2) takes intersection / detection
+// area as its overlap -- one select on the denominator, the division and every other operation are those of the unflagged row -- and stays available
+// however often it is matched.
 __global__ void __launch_bounds__(VE_THREADS) coco_match_kernel(VocIn a, CocoPar cp, const int* order, const int* gidx, const float4* gbox,
                                                                 const float* garea, unsigned char* matched, unsigned char* match_out) {
     const int lane = threadIdx.x & 63;
@@ -419,10 +442,12 @@ __global__ void __launch_bounds__(VE_THREADS) coco_match_kernel(VocIn a, CocoPar
                 const float ih = fmaxf(fminf(y2d, gb.z) - fmaxf(y1d, gb.x), 0.f);
                 const float iw = fmaxf(fminf(x2d, gb.w) - fmaxf(x1d, gb.y), 0.f);
                 const float inter = ih * iw;
+                const int fl = gt_flag(a, gidx[m]);
                 const float uni = ad + (gb.z - gb.x) * (gb.w - gb.y) - inter;
-                const float iou = uni > 0.f ? inter / uni : 0.f;
-                if (!active || matched[(size_t)m * RT + lane]) continue;
-                if (ag < lo || ag > hi) {
+                const float den = fl == 2 ? ad : uni;
+                const float iou = den > 0.f ? inter / den : 0.f;
+                if (!active || (fl != 2 && matched[(size_t)m * RT + lane])) continue;
+                if (fl || ag < lo || ag > hi) {
                     if (!(iou < best_i)) { best_i = iou; m_i = m; }
                 } else {
                     if (!(iou < best_n)) { best_n = iou; m_n = m; }
@@ -444,7 +469,6 @@ __global__ void __launch_bounds__(VE_THREADS) coco_match_kernel(VocIn a, CocoPar
 
 // a match code as a pair of counts: TP in the low word, FP in the high word (n <= 8 Mi: no carry between them); code 2 counts as neither
 __device__ __forceinline__ unsigned long long coco_packed(int code) { return code == 1 ? 1ull : (code == 0 ? (1ull << 32) : 0ull); }
-struct AddULL { __device__ unsigned long long operator()(unsigned long long x, unsigned long long y) const { return x + y; } };
 
 // x_k = np.linspace(0, 1, 101)[k] as numpy builds it: k * (1 / 100) in double, the last one exactly 1
 __device__ __forceinline__ double coco_recall_point(int k) { return k >= 100 ? 1.0 : (double)k * (1.0 / 100.0); }
@@ -558,7 +582,7 @@ int bits_for(long long maxval) {                                           // bi
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct VocLayout {
-    size_t idx[3], gidx[2], taken, hist, tot, ndet, total;
+    size_t idx[3], gidx[2], taken, hist, tot, bad, ndet, total;
     int nb;
 };
 VocLayout voc_layout(int D, int G, int C) {
@@ -572,6 +596,7 @@ VocLayout voc_layout(int D, int G, int C) {
     L.taken = off; off += align256((size_t)G);
     L.hist = off; off += align256((size_t)256 * L.nb * 4);
     L.tot = off; off += align256((size_t)256 * VE_MAX_PASSES * 4);
+    L.bad = L.tot + (size_t)256 * (VE_MAX_PASSES - 1) * 4;              // the last digit-total row: the sorts take 13 passes at the most (voc_sort)
     L.ndet = off; off += align256((size_t)(C + 1) * 4);
     L.total = off;
     return L;
@@ -583,14 +608,15 @@ bool voc_sizes_ok(int D, int G, int I, int C) {
 #define VOC_SIZES_MSG "voc_eval: num_det=%d num_gt=%d num_images=%d num_classes=%d outside the supported range (num_det <= %d, num_gt <= %d, " \
                       "1 <= num_images <= %d, 1 <= num_classes <= %d)"
 
-// init and the three sorts on `st`: what odtk_voc_eval and odtk_coco_eval share.  flags_out [D] is zeroed, npos [C] receives the GT rows per class.
+// init and the three sorts on `st`: what odtk_voc_eval and odtk_coco_eval share.  flags_out [D] is zeroed, npos [C] receives the flag-0 GT rows per
+// class, nign [C] (may be NULL) the flagged ones, the word at L.bad the check of the flag values (voc_flags_ok).
 struct VocSorted {
     int* rank;        // sort A: the per-class global rank order
     int* seg;         // sort B: (image, class) segments, rank order inside each
     const int* gt;    // sort G: GT indices by the (image, class) key
     int* ndet;        // valid detections per class
 };
-int voc_sort(const VocIn& a, const VocLayout& L, char* ws, unsigned char* flags_out, int* npos, hipStream_t st, VocSorted* out) {
+int voc_sort(const VocIn& a, const VocLayout& L, char* ws, unsigned char* flags_out, int* npos, int* nign, hipStream_t st, VocSorted* out) {
     const int D = a.D, G = a.G, I = a.I, C = a.C;
     int* idx[3] = {(int*)(ws + L.idx[0]), (int*)(ws + L.idx[1]), (int*)(ws + L.idx[2])};
     int* gidx[2] = {(int*)(ws + L.gidx[0]), (int*)(ws + L.gidx[1])};
@@ -600,12 +626,15 @@ int voc_sort(const VocIn& a, const VocLayout& L, char* ws, unsigned char* flags_
     int* ndet = (int*)(ws + L.ndet);
     if (int e = zero_async(tot, L.ndet + (size_t)(C + 1) * 4 - L.tot, st)) return e;          // tot .. ndet
     if (int e = zero_async(npos, (size_t)C * 4, st)) return e;
+    if (nign)
+        if (int e = zero_async(nign, (size_t)C * 4, st)) return e;
     const int nmax = D > G ? D : G;
     if (nmax > 0)
         hipLaunchKernelGGL(voc_init_kernel, dim3((nmax + VE_TILE - 1) / VE_TILE), dim3(VE_THREADS), 0, st, a, flags_out, idx[0], gidx[0], taken, ndet,
-                           npos);
+                           npos, nign, (int*)(ws + L.bad));
     // a stable LSD radix sort of an index list, 8 bits per pass: the first pass reads `src` and writes `a0`, the later ones alternate a0 -> a1 -> a0;
-    // returns the buffer that holds the result.  Passes: score 4 + class <= 2 + image <= 3 + GT <= 4 = 13 <= VE_MAX_PASSES digit-total rows
+    // returns the buffer that holds the result.  Passes: score 4 + class <= 2 + image <= 3 + GT <= 4 = 13 < VE_MAX_PASSES digit-total rows (the last
+    // row is never a pass's: its first word is L.bad)
     int pass = 0;
     auto radix = [&](int mode, int nbits, int n, int* src, int* a0, int* a1) -> int* {
         if (n == 0) return src;
@@ -653,6 +682,20 @@ CocoLayout coco_layout(int D, int G, int C, int RT) {
     return L;
 }
 bool coco_pairs_ok(int T, int R) { return T >= 1 && R >= 1 && (long long)T * R <= CE_MAX_PAIRS; }
+// after the launches of a call with gt_flags: the word that init left at L.bad (0, or 1 + the largest row index whose flag is above 2) back on the
+// host -- the one place where this file waits for the stream
+int voc_flags_ok(const char* who, const char* ws, const VocLayout& L, hipStream_t st) {
+    int bad = 0;
+#ifdef __HIPCC__
+    ODTK_CHECK_HIP(hipMemcpyAsync(&bad, ws + L.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    ODTK_CHECK_HIP(hipStreamSynchronize(st));
+#else                                                                       // the kernel source compiled for the host (tests): launches have run
+    (void)st;
+    memcpy(&bad, ws + L.bad, sizeof(int));
+#endif
+    ODTK_REQUIRE(bad == 0, "%s: gt_flags[%d] is above 2 (0 ordinary, 1 ignore, 2 crowd); the outputs are not valid", who, bad - 1);
+    return ODTK_OK;
+}
 #define COCO_PAIRS_MSG "coco_eval: num_thr=%d num_areas=%d outside the supported range (1 <= num_thr, 1 <= num_areas, num_thr * num_areas <= %d)"
 
 }  // namespace
@@ -671,6 +714,14 @@ extern "C" long long odtk_voc_eval_workspace_bytes(int num_det, int num_gt, int 
 extern "C" int odtk_voc_eval(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
                              const int* gt_img, int num_gt, int num_images, int num_classes, float iou_thr, int metric, void* workspace,
                              unsigned char* tp_out, int* npos_out, double* ap_out, void* stream) {
+    return odtk_voc_eval_flags(scores, boxes, det_cls, det_img, num_det, gt_rows, gt_img, nullptr, num_gt, num_images, num_classes, iou_thr, metric,
+                               workspace, tp_out, npos_out, nullptr, ap_out, stream);
+}
+
+extern "C" int odtk_voc_eval_flags(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                                   const int* gt_img, const unsigned char* gt_flags, int num_gt, int num_images, int num_classes, float iou_thr,
+                                   int metric, void* workspace, unsigned char* match_out, int* npos_out, int* nign_out, double* ap_out, void* stream) {
+    unsigned char* tp_out = match_out;
     ODTK_REQUIRE(voc_sizes_ok(num_det, num_gt, num_images, num_classes), VOC_SIZES_MSG, num_det, num_gt, num_images, num_classes, VE_MAX_DET,
                  VE_MAX_GT, VE_MAX_IMAGES, VE_MAX_CLASSES);
     ODTK_REQUIRE(metric == 0 || metric == 1, "voc_eval: metric %d (0 = voc07 11-point, 1 = area)", metric);
@@ -682,15 +733,15 @@ extern "C" int odtk_voc_eval(const float* scores, const float* boxes, const int*
     hipStream_t st = (hipStream_t)stream;
     VocIn a;
     a.scores = scores; a.boxes = boxes; a.det_cls = det_cls; a.det_img = det_img; a.gt = gt_rows; a.gt_img = gt_img;
-    a.D = D; a.G = G; a.I = I; a.C = C;
+    a.D = D; a.G = G; a.I = I; a.C = C; a.gfl = G > 0 ? gt_flags : nullptr;
     VocSorted s;
-    if (int e = voc_sort(a, L, (char*)workspace, tp_out, npos_out, st, &s)) return e;
+    if (int e = voc_sort(a, L, (char*)workspace, tp_out, npos_out, nign_out, st, &s)) return e;
     if (D > 0)
         hipLaunchKernelGGL(voc_match_kernel, dim3((D + VE_THREADS - 1) / VE_THREADS), dim3(VE_THREADS), 0, st, a, s.seg, s.gt,
                            (unsigned char*)workspace + L.taken, iou_thr, tp_out);
     hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(VE_THREADS), 0, st, a, s.rank, s.ndet, npos_out, tp_out, metric, ap_out);
     ODTK_LAUNCH_CHECK();
-    return ODTK_OK;
+    return a.gfl ? voc_flags_ok("voc_eval", (const char*)workspace, L, st) : ODTK_OK;
 }
 
 extern "C" long long odtk_coco_eval_workspace_bytes(int num_det, int num_gt, int num_images, int num_classes, int num_thr, int num_areas) {
@@ -709,6 +760,14 @@ extern "C" int odtk_coco_eval(const float* scores, const float* boxes, const int
                               const int* gt_img, int num_gt, int num_images, int num_classes, const float* iou_thr, int num_thr,
                               const float* area_rng, int num_areas, int max_dets, void* workspace, unsigned char* match_out, int* npos_out,
                               double* ap_out, double* recall_out, void* stream) {
+    return odtk_coco_eval_flags(scores, boxes, det_cls, det_img, num_det, gt_rows, gt_img, nullptr, num_gt, num_images, num_classes, iou_thr, num_thr,
+                                area_rng, num_areas, max_dets, workspace, match_out, npos_out, ap_out, recall_out, stream);
+}
+
+extern "C" int odtk_coco_eval_flags(const float* scores, const float* boxes, const int* det_cls, const int* det_img, int num_det, const float* gt_rows,
+                                    const int* gt_img, const unsigned char* gt_flags, int num_gt, int num_images, int num_classes,
+                                    const float* iou_thr, int num_thr, const float* area_rng, int num_areas, int max_dets, void* workspace,
+                                    unsigned char* match_out, int* npos_out, double* ap_out, double* recall_out, void* stream) {
     ODTK_REQUIRE(voc_sizes_ok(num_det, num_gt, num_images, num_classes), VOC_SIZES_MSG, num_det, num_gt, num_images, num_classes, VE_MAX_DET,
                  VE_MAX_GT, VE_MAX_IMAGES, VE_MAX_CLASSES);
     ODTK_REQUIRE(coco_pairs_ok(num_thr, num_areas), COCO_PAIRS_MSG, num_thr, num_areas, CE_MAX_PAIRS);
@@ -722,7 +781,7 @@ extern "C" int odtk_coco_eval(const float* scores, const float* boxes, const int
     hipStream_t st = (hipStream_t)stream;
     VocIn a;
     a.scores = scores; a.boxes = boxes; a.det_cls = det_cls; a.det_img = det_img; a.gt = gt_rows; a.gt_img = gt_img;
-    a.D = D; a.G = G; a.I = num_images; a.C = C;
+    a.D = D; a.G = G; a.I = num_images; a.C = C; a.gfl = G > 0 ? gt_flags : nullptr;
     CocoPar cp;
     for (int k = 0; k < CE_MAX_PAIRS; ++k) {
         cp.thr[k] = k < T ? iou_thr[k] : 0.f;
@@ -731,7 +790,7 @@ extern "C" int odtk_coco_eval(const float* scores, const float* boxes, const int
     }
     cp.T = T; cp.R = R; cp.max_dets = max_dets;
     VocSorted s;
-    if (int e = voc_sort(a, L.v, ws, (unsigned char*)(ws + L.flags), (int*)(ws + L.npos_all), st, &s)) return e;
+    if (int e = voc_sort(a, L.v, ws, (unsigned char*)(ws + L.flags), (int*)(ws + L.npos_all), nullptr, st, &s)) return e;
     if (int e = zero_async(npos_out, (size_t)R * C * 4, st)) return e;
     float4* gbox = (float4*)(ws + L.gbox);
     float* garea = (float*)(ws + L.garea);
@@ -744,5 +803,5 @@ extern "C" int odtk_coco_eval(const float* scores, const float* boxes, const int
     }
     hipLaunchKernelGGL(coco_ap_kernel, dim3(C, RT), dim3(VE_THREADS), 0, st, a, T, s.rank, s.ndet, npos_out, match_out, ap_out, recall_out);
     ODTK_LAUNCH_CHECK();
-    return ODTK_OK;
+    return a.gfl ? voc_flags_ok("coco_eval", ws, L.v, st) : ODTK_OK;
 }

@@ -769,6 +769,15 @@ def voc_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_c
          float(iou_thr), VOC_METRICS[metric], _p(ws), e(tp), _p(npos), _p(ap), _stream())
 
 
+def voc_eval_flags(scores, boxes, det_cls, det_img, gt_rows, gt_img, gt_flags, num_images, num_classes, iou_thr, metric, ws, match, npos, nign, ap):
+    """voc_eval with gt_flags u8[G] (0 ordinary, 1 ignore, 2 crowd; None = no flags) -> match u8[D] (0 FP, 1 TP, 2 ignored), npos / nign i32[C]
+    (nign may be None), ap f64[C]; waits for the stream when gt_flags is given (include/odtk.h)"""
+    D, G = scores.shape[0], gt_rows.shape[0]
+    e = lambda t: _p(t) if t is not None and t.numel() else None      # noqa: E731 -- an empty side passes NULL
+    call("odtk_voc_eval_flags", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), e(gt_flags), G, int(num_images),
+         int(num_classes), float(iou_thr), VOC_METRICS[metric], _p(ws), e(match), _p(npos), None if nign is None else _p(nign), _p(ap), _stream())
+
+
 # ---------------------------------------------------------------- evaluation: COCO-style AP (csrc/voc_eval.hip, odtk_coco_eval)
 def coco_eval_workspace(D, G, I, C, T, R, device):
     n = int(_lib.load().odtk_coco_eval_workspace_bytes(D, G, I, C, T, R))
@@ -787,6 +796,18 @@ def coco_eval(scores, boxes, det_cls, det_img, gt_rows, gt_img, num_images, num_
     call("odtk_coco_eval", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), G, int(num_images), int(num_classes),
          C.c_void_p(thr.ctypes.data), thr.shape[0], C.c_void_p(rng.ctypes.data), rng.shape[0], int(max_dets), _p(ws), e(match), _p(npos), _p(ap),
          _p(recall), _stream())
+
+
+def coco_eval_flags(scores, boxes, det_cls, det_img, gt_rows, gt_img, gt_flags, num_images, num_classes, iou_thr, area_rng, max_dets, ws, match, npos, ap,
+                    recall):
+    """coco_eval with gt_flags u8[G] (0 ordinary, 1 ignore, 2 crowd; None = no flags); waits for the stream when gt_flags is given (include/odtk.h)"""
+    D, G = scores.shape[0], gt_rows.shape[0]
+    thr = np.ascontiguousarray(iou_thr, np.float32).reshape(-1)
+    rng = np.ascontiguousarray(area_rng, np.float32).reshape(-1, 2)
+    e = lambda t: _p(t) if t is not None and t.numel() else None      # noqa: E731 -- an empty side passes NULL
+    call("odtk_coco_eval_flags", e(scores), e(boxes), e(det_cls), e(det_img), D, e(gt_rows), e(gt_img), e(gt_flags), G, int(num_images),
+         int(num_classes), C.c_void_p(thr.ctypes.data), thr.shape[0], C.c_void_p(rng.ctypes.data), rng.shape[0], int(max_dets), _p(ws), e(match),
+         _p(npos), _p(ap), _p(recall), _stream())
 
 
 # ---------------------------------------------------------------- evaluation: classification metrics (csrc/classify.hip)

@@ -8,6 +8,10 @@
     get_generator                       shards -> shuffle buffer -> batches -> decode -> odtk.augment.Augmentor: the object a model takes as
                                         data_provider['train_generator'] (or 'val_generator', with a config that has no random part)
 
+Beyond the reference: the annotation's `<difficult>` (the PASCAL VOC protocol does not count such objects, voc_eval.py).  With with_difficult=True
+dataset2tfrecord writes a fourth bytes_list feature `difficult` (uint8[G], next to `ground_truth`; readers that do not know it skip it) and
+get_generator yields [B, pad, 6] ground truth whose last column is the flag of the box in that row.  Without it records and batches are the reference's.
+
 Where this differs from the reference, on purpose:
   - dataset2tfrecord writes EVERY annotation.  The reference's shard size `int(ceil(len(xmllist)) / float(total_shards))` rounds down and silently drops
     up to total_shards - 1 annotations at the end of the list.
@@ -100,11 +104,17 @@ def _feature(key: str, value: bytes) -> bytes:
     return _pb_bytes(1, key.encode()) + _pb_bytes(2, _pb_bytes(1, _pb_bytes(1, value)))
 
 
-def encode_example(image: bytes, shape, ground_truth) -> bytes:
-    """the reference's Example (tfrecord_voc_utils.xml_to_example): Example{features = 1 -> Features{feature = 1 (repeated map entry)}}"""
+def encode_example(image: bytes, shape, ground_truth, difficult=None) -> bytes:
+    """the reference's Example (tfrecord_voc_utils.xml_to_example): Example{features = 1 -> Features{feature = 1 (repeated map entry)}}; difficult
+    (uint8[G], one flag per ground-truth row) adds the feature `difficult` behind them"""
     shape = np.asarray(shape, np.int32).reshape(3)
     gt = np.asarray(ground_truth, np.float32).reshape(-1, 5)
     entries = [_feature('image', bytes(image)), _feature('shape', shape.tobytes()), _feature('ground_truth', gt.tobytes())]
+    if difficult is not None:
+        flags = np.asarray(difficult, np.uint8).reshape(-1)
+        if flags.shape[0] != gt.shape[0]:
+            raise ValueError(f'difficult holds {flags.shape[0]} flags for {gt.shape[0]} ground-truth rows')
+        entries.append(_feature('difficult', flags.tobytes()))
     return _pb_bytes(1, b''.join(_pb_bytes(1, e) for e in entries))
 
 
@@ -127,10 +137,11 @@ def _example_features(record: bytes):
 
 
 def parse_example(record: bytes) -> dict:
-    """{'image': bytes, 'shape': int32[3], 'ground_truth': float32[G, 5]}; map entries in any order, unknown features ignored"""
+    """{'image': bytes, 'shape': int32[3], 'ground_truth': float32[G, 5]} and, when the record has the feature, 'difficult': uint8[G]; map entries in any
+    order, unknown features ignored"""
     feats = {}
     for key, value in _example_features(record):
-        if key in ('image', 'shape', 'ground_truth') and value is not None:
+        if key in ('image', 'shape', 'ground_truth', 'difficult') and value is not None:
             for f4, wt4, blist in _pb_parse(value):
                 if f4 == 1 and wt4 == 2:                      # bytes_list
                     vals = [v for f5, wt5, v in _pb_parse(blist) if f5 == 1 and wt5 == 2]
@@ -141,32 +152,44 @@ def parse_example(record: bytes) -> dict:
         raise ValueError(f'Example without the bytes_list feature(s) {missing}')
     if len(feats['shape']) != 12 or len(feats['ground_truth']) % 20:
         raise ValueError(f"Example with a shape of {len(feats['shape'])} bytes / ground truth of {len(feats['ground_truth'])} bytes (int32[3] / float32[G, 5])")
-    return {'image': feats['image'], 'shape': np.frombuffer(feats['shape'], np.int32).copy(),
-            'ground_truth': np.frombuffer(feats['ground_truth'], np.float32).reshape(-1, 5).copy()}
+    out = {'image': feats['image'], 'shape': np.frombuffer(feats['shape'], np.int32).copy(),
+           'ground_truth': np.frombuffer(feats['ground_truth'], np.float32).reshape(-1, 5).copy()}
+    if 'difficult' in feats:
+        if len(feats['difficult']) != out['ground_truth'].shape[0]:
+            raise ValueError(f"Example with {len(feats['difficult'])} difficult flags for {out['ground_truth'].shape[0]} ground-truth rows")
+        out['difficult'] = np.frombuffer(feats['difficult'], np.uint8).copy()
+    return out
 
 
 # --------------------------------------------------------------------------------------------------- VOC annotations
-def xml_to_example(xmlpath, imgpath) -> bytes:
+def xml_to_example(xmlpath, imgpath, with_difficult=False) -> bytes:
     """one VOC annotation + its JPEG file (read, not decoded) -> serialized Example.  Like the reference's xpath('//object') this takes EVERY `object`
-    element of the document, at any depth; the box is the object's own `bndbox` child."""
+    element of the document, at any depth; the box is the object's own `bndbox` child.  with_difficult: the object's `<difficult>` (absent or 0 -> 0,
+    1 -> 1, anything else a ValueError naming the file) goes into the feature `difficult`."""
     root = ET.parse(xmlpath).getroot()
     with open(os.path.join(imgpath, root.find('filename').text), 'rb') as f:
         image = f.read()
     size = root.find('size')
     shape = [int(size.find(k).text) for k in ('height', 'width', 'depth')]
-    rows = []
+    rows, difficult = [], []
     for obj in root.iter('object'):
         box = obj.find('bndbox')
         rows.append([float(box.find(k).text) for k in ('ymin', 'ymax', 'xmin', 'xmax')] + [classname_to_ids[obj.find('name').text]])
-    return encode_example(image, shape, np.asarray(rows, np.float32).reshape(-1, 5))
+        if with_difficult:
+            tag = obj.find('difficult')
+            text = '0' if tag is None else (tag.text or '').strip()
+            if text not in ('0', '1'):
+                raise ValueError(f'{xmlpath}: <difficult>{text}</difficult> of object {len(rows) - 1} is neither 0 nor 1')
+            difficult.append(int(text))
+    return encode_example(image, shape, np.asarray(rows, np.float32).reshape(-1, 5), np.asarray(difficult, np.uint8) if with_difficult else None)
 
 
-def dataset2tfrecord(xml_dir, img_dir, output_dir, name, total_shards=5):
+def dataset2tfrecord(xml_dir, img_dir, output_dir, name, total_shards=5, with_difficult=False):
     """Converts a VOC directory: the `*.xml` annotations of xml_dir, in sorted order, with their pictures from img_dir, into total_shards record files
     `<name>_<k>-of-<n>.tfrecord` (k from 1, both five digits: the reference's file names) under output_dir; returns the paths in shard order.
     ALL annotations are written: consecutive runs of ceil(n / total_shards), so the last shards may be short or empty (the reference's arithmetic rounds
     down and drops up to total_shards - 1 annotations, see the module docstring).  Records are added to a directory that already holds files; a warning
-    says so."""
+    says so.  with_difficult: every record also carries the objects' `<difficult>` flags (xml_to_example); without it the records are the reference's."""
     total_shards = int(total_shards)
     if total_shards < 1:
         raise ValueError(f'total_shards must be >= 1, not {total_shards}')
@@ -179,7 +202,7 @@ def dataset2tfrecord(xml_dir, img_dir, output_dir, name, total_shards=5):
     for k, path in enumerate(paths):
         with TFRecordWriter(path) as writer:
             for annotation in annotations[k * run: (k + 1) * run]:
-                writer.write(xml_to_example(annotation, img_dir))
+                writer.write(xml_to_example(annotation, img_dir, with_difficult))
     return paths
 
 
@@ -347,6 +370,30 @@ def _voc_payload(examples):
     return [torch.from_numpy(e['ground_truth']) for e in examples]
 
 
+FLAG_STRIDE = 1024          # the evaluators' class cap: class + FLAG_STRIDE * flag is exact in f32 and splits again without loss
+
+
+def _voc_payload_difficult(examples):
+    """the ground truths with each row's flag folded into its class column (class + FLAG_STRIDE * flag): odtk_augment_boxes drops and compacts rows and
+    carries that column through unchanged, so the flag arrives in whatever row its box ends up in.  A record without the feature: flags 0."""
+    out = []
+    for e in examples:
+        gt = e['ground_truth'].copy()
+        if 'difficult' in e:
+            gt[:, 4] += np.float32(FLAG_STRIDE) * e['difficult'].astype(np.float32)
+        out.append(torch.from_numpy(gt))
+    return out
+
+
+def _split_flag_column(gt):
+    """[N, pad, 5] with class + FLAG_STRIDE * flag in column 4 -> [N, pad, 6]: class, flag; padding rows (-1) stay -1 in both"""
+    folded = gt[..., 4]
+    real = folded >= 0
+    flag = torch.where(real, torch.floor(folded / FLAG_STRIDE), torch.full_like(folded, -1))
+    cls = torch.where(real, folded - FLAG_STRIDE * flag, folded)
+    return torch.cat([gt[..., :4], cls[..., None], flag[..., None]], -1)
+
+
 def _worker(paths, batch_size, buffer_size, seed, verify, decoder, out_q, stop, parse=parse_example, extra=_voc_payload, refusal=None, skipped=None):
     """CPU work only (file reads, CRCs, protobuf, Huffman decoding): never a GPU call.  Puts (host batch, extra(examples)) or an exception.
     parse / extra: record -> example dict with an 'image', examples of a batch -> what travels with the pictures (VOC: the ground truths).
@@ -450,14 +497,20 @@ class VOCGenerator:
 
     def _worker_options(self):
         """keyword arguments of _worker: the record layout of this generator (imagenet_data.ImageNetGenerator has its own)"""
-        return {}
+        return {'extra': _voc_payload_difficult} if self.with_difficult else {}
 
     def _finish(self, images, gts):
         """the consumer's last stage: decoded pictures + what the worker sent with them -> one item of the stream"""
-        return self._augmentor(images, gts)
+        if not self.with_difficult:
+            return self._augmentor(images, gts)
+        images, gt = self._augmentor(images, gts)
+        return images, _split_flag_column(gt)
+
+    with_difficult = False
 
     def __init__(self, tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, decoder=None,
-                 augmentor=None):
+                 augmentor=None, with_difficult=False):
+        self.with_difficult = bool(with_difficult)
         self.tfrecords = [tfrecords] if isinstance(tfrecords, (str, os.PathLike)) else list(tfrecords)
         self.batch_size, self.buffer_size, self.prefetch, self.verify, self.seed = int(batch_size), max(1, int(buffer_size)), int(prefetch), verify, seed
         assert self.batch_size > 0 and self.tfrecords
@@ -477,12 +530,16 @@ class VOCGenerator:
         return it
 
 
-def get_generator(tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, **hooks):
+def get_generator(tfrecords, batch_size, buffer_size, image_preprocess_config, device='cuda:0', seed=None, prefetch=2, verify=True, with_difficult=False,
+                  **hooks):
     """tfrecord_voc_utils.get_generator: `.tfrecord` shards -> endless batches ([B, H, W, 3] f32 pictures, [B, pad_truth_to, 5] ground truth), exactly what
     odtk.augment.Augmentor returns with ground truth (image_preprocess_config is the reference's image_augmentor_config and needs pad_truth_to).
     Order of the stages as in the reference: records in file order -> shuffle buffer of buffer_size (shuffle_stream) -> batches of batch_size, the
     remainder of a pass dropped -> repeated without end.  Each iter() of the returned object restarts the stream (and ends the previous one).  A daemon
     thread reads, parses and Huffman-decodes up to `prefetch` batches ahead; upload, reconstruction and augmentation run on the consumer's thread and
     current stream.  A record whose JPEG the decoder refuses raises JpegError('record <index>: <message>') from next().  `seed` fixes the shuffle and
-    the augmentor's draws.  hooks (tests): decoder=, augmentor= replace the two device stages."""
-    return VOCGenerator(tfrecords, batch_size, buffer_size, image_preprocess_config, device, seed, prefetch, verify, **hooks)
+    the augmentor's draws.  with_difficult=True: ground truth [B, pad_truth_to, 6], column 5 the `difficult` flag (0 / 1; 0 for records written without
+    it; -1 in padding rows) of the box that the augmentor left in that row -- what odtk.evaluate() takes; training code keeps the default.
+    hooks (tests): decoder=, augmentor= replace the two device stages."""
+    return VOCGenerator(tfrecords, batch_size, buffer_size, image_preprocess_config, device, seed, prefetch, verify, with_difficult=with_difficult,
+                        **hooks)

@@ -8,6 +8,10 @@
   * --coco: only the COCO-style leg on the VOC07-test sized input (odtk.COCOEvaluator, default 10 thresholds x 4 area ranges, max_dets 100): result()
     wall time, the kernels alone (odtk_coco_eval, HIP events), ten VOCEvaluator.result() calls at the ten thresholds on the same data (what the
     ten-threshold number cost before odtk_coco_eval existed) and the NumPy restatement (tests/coco_eval_ref.evaluate_fast).
+  * --flags: only the ground-truth-flag leg on the VOC07-test sized input with VOC07-test's share of `difficult` rows (2 944 of 14 976):
+    odtk_voc_eval_flags / odtk_coco_eval_flags next to odtk_voc_eval / odtk_coco_eval on the same uploaded tensors in the same process, the calls
+    interleaved, every repetition timed by its own pair of HIP events (median, min, max).  The flagged calls end with the read-back of the flag check
+    (a 4-byte copy and a stream synchronisation inside the entry point), which the events include.
 Per-kernel times: run `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/eval_bench.py --kernels-only` separately."""
 import argparse
 import json
@@ -132,6 +136,53 @@ def coco_leg(dev, reps):
     return row
 
 
+def flags_leg(dev, reps):
+    C = 20
+    dets, gts = synthetic(0, 4952, C, 100, 2.4, None)
+    G = sum(len(g) for g in gts)
+    rng = np.random.default_rng(5)
+    difficult = np.zeros(G, np.uint8)
+    difficult[rng.permutation(G)[: round(G * 2944 / 14976)]] = 1
+    ev = odtk.COCOEvaluator(C, device=dev)
+    at = 0
+    for d, g in zip(dets, gts):
+        ev.add(list(d), g, flags=difficult[at: at + len(g)])
+        at += len(g)
+    args, _, gfl, nign_host = ev._upload(True)
+    D, I = args[0].shape[0], ev.num_images
+    T, Rn = ev.iou_thresholds.shape[0], ev.area_ranges.shape[0]
+    ws_v, ws_c = ops.voc_eval_workspace(D, G, I, C, dev), ops.coco_eval_workspace(D, G, I, C, T, Rn, dev)
+    tp = torch.empty(D, dtype=torch.uint8, device=dev)
+    npos, nign = (torch.empty(C, dtype=torch.int32, device=dev) for _ in range(2))
+    ap = torch.empty(C, dtype=torch.float64, device=dev)
+    match = torch.empty(Rn, T, D, dtype=torch.uint8, device=dev)
+    npos_c = torch.empty(Rn, C, dtype=torch.int32, device=dev)
+    ap_c, rec_c = (torch.empty(Rn, T, C, dtype=torch.float64, device=dev) for _ in range(2))
+    runs = {
+        'voc_eval': lambda: ops.voc_eval(*args, I, C, 0.5, 'voc07', ws_v, tp, npos, ap),
+        'voc_eval_flags': lambda: ops.voc_eval_flags(*args, gfl, I, C, 0.5, 'voc07', ws_v, tp, npos, nign, ap),
+        'coco_eval': lambda: ops.coco_eval(*args, I, C, ev.iou_thresholds, ev.area_ranges, ev.max_dets, ws_c, match, npos_c, ap_c, rec_c),
+        'coco_eval_flags': lambda: ops.coco_eval_flags(*args, gfl, I, C, ev.iou_thresholds, ev.area_ranges, ev.max_dets, ws_c, match, npos_c, ap_c,
+                                                       rec_c),
+    }
+    times = {k: [] for k in runs}
+    for f in runs.values():
+        f()
+    torch.cuda.synchronize()
+    for _ in range(reps):                                              # interleaved: a drift of the clock hits all four alike
+        for k, f in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1))
+    row = {'images': I, 'detections': D, 'gt_rows': G, 'flagged_rows': int(difficult.sum()), 'reps': reps, 'ignored_per_class_sum': int(nign_host.sum())}
+    for k, v in times.items():
+        row[k + '_ms'] = {'median': float(np.median(v)), 'min': float(np.min(v)), 'max': float(np.max(v))}
+    return row
+
+
 def time_numpy(dets, gts, C):
     t = time.perf_counter()
     R.evaluate_fast(dets, gts, C)
@@ -179,10 +230,14 @@ def main():
     ap.add_argument('--e2e-images', type=int, default=256)
     ap.add_argument('--kernels-only', action='store_true', help='a few kernel runs of both inputs (for rocprofv3 --kernel-trace --stats)')
     ap.add_argument('--coco', action='store_true', help='only the COCO-style leg (odtk.COCOEvaluator against ten VOC passes and the NumPy restatement)')
+    ap.add_argument('--flags', action='store_true', help='only the flag leg: the _flags entry points next to the unflagged ones, VOC07-test sized')
     a = ap.parse_args()
     torch.set_num_threads(16)
     os.environ.setdefault('OMP_NUM_THREADS', '16')
     dev = torch.device('cuda:0')
+    if a.flags:
+        print(json.dumps({'flags_voc07': flags_leg(dev, a.reps)}))
+        return
     if a.coco:
         print(json.dumps({'coco_voc07': coco_leg(dev, a.reps)}))
         return
