@@ -10,7 +10,7 @@ Reference: /root/reference/CenterNet.py
                                            term, moved by weight decay only); DLA aggregation (one activation feeds several sums);
                                            4x4 / stride-2 transposed convolutions; 2x2 max and average pooling
   * loss, optimizer ...................... :136-157 (odtk_centernet_loss; mean over images + wd * l2(all trainables); AdamOptimizer)
-  * inference ............................ :158-185 (heads.centernet_detect: 3x3 peak test + top-k, no NMS)
+  * inference ............................ :158-185 (heads.CenterNetBatched: 3x3 peak test + top-k, no NMS)
   * train / test / checkpoints ........... :298-323
 Layers c0 .. c65 in creation order (layer k = conv k + batch norm k), one flat f32 parameter buffer + Adam's two moment buffers.
 A transposed convolution runs as the DGRAD of the stride-2 conv it is the gradient of (its kernel stored as that conv's filter
@@ -31,7 +31,6 @@ import torch
 from . import heads, ops
 from ._lib import BF16
 from .base import DetectorBase
-from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN = (0.485, 0.456, 0.406)                                  # CenterNet.py:52-53
@@ -84,7 +83,7 @@ class _Act:
         self.g = None                                          # gradient buffer (train mode, allocated by _build_backward)
 
 
-class CenterNet(EvaluateMixin, F32Warmup, DetectorBase):
+class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
     OPT_BUFFERS = ('M1', 'M2')                                 # Adam's m and v
     OPT_BLOB_KEYS = ('adam_m', 'adam_v')
     PROGRESS_FROM = 1                                          # CenterNet.py's epoch loop prints i + 1
@@ -397,33 +396,16 @@ class CenterNet(EvaluateMixin, F32Warmup, DetectorBase):
         return self.loss_parts[:, 3].mean() + self.weight_decay * self.l2_sum          # CenterNet.py:152-153 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
-    NATIVE_TEST_IMAGES = True
-    _tail_batched = None
-
-    def test_images(self, images):
-        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then odtk_centernet_decode_batched (one workgroup per image for the peak
-        test + top-k) and one read-back (heads.CenterNetBatched).  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
-        n = self._stage_test_images(images)
-        self._forward(False, normalize=bool(self.config.get('test_normalize', False)))       # the reference's quirk, as in test_one_image
-        t = self._tail_batched
-        if t is None:
-            t = self._tail_batched = heads.CenterNetBatched(self.batch_size, self.kp_act.H, self.kp_act.W, self.top_k_results_output, self.dev)
-        return t(self.keypoints, self.offset, self.size, self.score_threshold, STRIDE, n)
-
-    def test_one_image(self, images):
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self.test_images(images)[0]
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
+    def _forward_test(self):
         # Reference quirk, reproduced by default: test mode re-binds self.images to the normalised tensor and feeds THAT one
         # (CenterNet.py:66-67, :312), so fed pixels bypass the (x / 255 - mean) / std transform.
         self._forward(False, normalize=bool(self.config.get('test_normalize', False)))
-        scores, bbox, cid = heads.centernet_detect(self.keypoints[0], self.offset[0], self.size[0], self.score_threshold,
-                                                   self.top_k_results_output, STRIDE, self.loss_ws)
-        return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
+
+    def _make_tail(self):
+        return heads.CenterNetBatched(self.batch_size, self.kp_act.H, self.kp_act.W, self.top_k_results_output, self.dev)
+
+    def _launch_tail(self, t):
+        t.launch(self.keypoints, self.offset, self.size, self.score_threshold, STRIDE)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
     def export_tf_variables(self):

@@ -2,14 +2,17 @@
 per-class NMS (the SSD300 NMS path) -> [scores f32[K], bbox f32[K,4] y1x1y2x2 px, class_id i32[K]], i.e. what each class
 stores in `self.detection_pred` (RetinaNet.py:224-256, YOLOv3.py:320-368, FCOS.py:197-265, CenterNet.py:159-185, RefineDet.py:189-230);
 for RefineDet also the training-side chain matching -> ARM hard-negative mining -> two-stage loss (`refinedet_loss`).
-Inputs are the head outputs of ONE image as device tensors; `BatchedTail` is the same tail for N images per launch (test_images) and `CenterNetBatched`
-CenterNet's peak test + top-k for N images.  Native test_images: SSD300, SSD512, YOLOv3, RetinaNet, CenterNet, RefineDet320, PFPNetR; FCOS, YOLOv2 and
-Light-Head R-CNN loop over test_one_image.  Product path: no CPU fallback, no use of the test oracles."""
+ONE inference path for SSD300, SSD512, YOLOv3, RetinaNet, CenterNet, RefineDet320 and PFPNetR: `BatchedInference` (test_images: one forward pass at
+N = test_batch_size, the class's decode, `BatchedTail` -- CenterNet: `CenterNetBatched` -- and one read-back; test_one_image is that path with one image).
+FCOS, YOLOv2 and Light-Head R-CNN keep a single-image test_one_image on `_per_class_nms` (fcos_detect, yolov2_detect, lhrcnn.py) and the loop of
+voc_eval.EvaluateMixin as test_images.  Product path: no CPU fallback, no use of the test oracles."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
+from .voc_eval import EvaluateMixin
 
 NMS_MAX_CANDIDATES = 32768          # odtk_nms_batched: boxes per problem
 
@@ -46,12 +49,19 @@ class BatchedTail:
     -> NMS of N * num_classes problems in one launch chain (odtk_nms_image_class) -> detection pack (odtk_detection_pack) -> ONE read-back per batch (the
     per-image counts, their scan and the packed rows, through a pinned host buffer).  Per image the result is what `_per_class_nms` returns for that image
     alone, bit for bit: the same NMS kernels on the same operands, the same order (ascending class id, NMS pick order inside).  Buffers are allocated once
-    per (N, A, num_classes, max_boxes).  conf [N, A, ld] scores (classes in the first num_classes columns), boxes [N, A, 4], cand [N, A, ld] uint8."""
+    per (N, A, num_classes, max_boxes).  conf [N, A, ld] scores (classes in the first num_classes columns), boxes [N, A, 4], cand [N, A, ld] uint8.
+    The tail also holds what a class's decode writes for it: self.conf [N, A, nc], self.boxes [N, A, 4], self.keep u8 [N, A], self.cand u8 [N, A, nc];
+    bool_cand (YOLOv3: the threshold is one torch.ge): cand is a bool tensor and there is no keep.  `launch_own` runs the tail on them."""
 
-    def __init__(self, N, A, num_classes, max_boxes, device):
+    def __init__(self, N, A, num_classes, max_boxes, device, bool_cand=False):
         self.N, self.A, self.nc, self.max_boxes = int(N), int(A), int(num_classes), int(max_boxes)
         dev = self.dev = torch.device(device)
-        N, nc = self.N, self.nc
+        N, A, nc = self.N, self.A, self.nc
+        self.conf = torch.zeros(N, A, nc, device=dev)
+        self.boxes = torch.zeros(N, A, 4, device=dev)
+        self.cand = torch.zeros(N, A, nc, dtype=torch.bool if bool_cand else torch.uint8, device=dev)
+        if not bool_cand:
+            self.keep = torch.zeros(N, A, dtype=torch.uint8, device=dev)
         cap = self.cap = max(self.max_boxes, 1)
         i32 = dict(dtype=torch.int32, device=dev)
         self.compact = self.A > NMS_MAX_CANDIDATES
@@ -93,6 +103,10 @@ class BatchedTail:
                                 self.out_idx, self.cap, self.out_cnt)
         ops.detection_pack(self.out_idx, self.out_cnt, conf, boxes, self.counts, self.offsets, self.scores, self.bbox, self.class_id)
 
+    def launch_own(self, iou_thr):
+        """launch() on the decode outputs the tail holds itself"""
+        self.launch(self.conf, self.boxes, self.cand.view(torch.uint8), iou_thr)
+
     def read(self, n_images=None):
         """the one read-back: list of [scores f32[K], bbox f32[K, 4], class_id i32[K]] (numpy) of the first n_images images"""
         n_images = self.N if n_images is None else int(n_images)
@@ -120,7 +134,7 @@ class BatchedTail:
 
 class CenterNetBatched:
     """CenterNet's tail for N images at once: odtk_centernet_decode_batched (sigmoid / arg-max over all pixels, then one workgroup per image for the 3x3 peak
-    test, the threshold and the top-k) -> ONE read-back per batch through a pinned host buffer.  Per image the result is what `centernet_detect` returns for
+    test, the threshold and the top-k) -> ONE read-back per batch through a pinned host buffer.  Per image the result is what odtk_centernet_decode gives for
     that image alone, bit for bit.  One buffer of 4-byte words travels back: counts [N] | scores [N, top_k] | bbox [N, top_k, 4] | class_id [N, top_k]; rows
     behind an image's count are never read."""
 
@@ -164,10 +178,53 @@ class CenterNetBatched:
         return self.read(n_images)
 
 
-def retina_detect(pconf, pbox, anchors_yx, anchors_hw, score_thr, max_boxes, iou_thr):
-    """RetinaNet.py:224-256.  pconf [A, C] logits (last class = background), pbox [A, 4] = (dy, dx, log h, log w)."""
-    conf, boxes, _, cand = ops.retina_decode(pconf, pbox, anchors_yx, anchors_hw, score_thr)
-    return _per_class_nms(conf, boxes, cand, pconf.shape[1] - 1, max_boxes, iou_thr)
+class BatchedInference(EvaluateMixin):
+    """The inference surface of the classes with a batched tail -- SSD300, SSD512, YOLOv3, RetinaNet, CenterNet, RefineDet320, PFPNetR: test_images is
+    stage -> ONE forward pass at N = test_batch_size -> the class's decode into its tail (BatchedTail / CenterNetBatched, built with the first call) -> one
+    read-back, and test_one_image is test_images of one image.  A class supplies three hooks:
+      _forward_test()    the test-mode forward pass with the reference's feed quirk;
+      _make_tail()       the tail for self.batch_size image slots;
+      _launch_tail(t)    the decode launch(es) and t's own launch, no synchronisation."""
+
+    NATIVE_TEST_IMAGES = True
+    _tail_batched = None
+
+    @staticmethod
+    def _test_batch_size(config):
+        """config['test_batch_size']: optional, an integer >= 1 (default 1), read in test mode only: the number of image slots of the test-mode buffers"""
+        b = config.get('test_batch_size', 1)
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
+            raise ValueError(f"test_batch_size must be an integer >= 1, not {b!r}")
+        return int(b)
+
+    def _stage_test_images(self, images):
+        """the n <= test_batch_size images into the first n slots of self.images (the tail slots keep what they held: computed, discarded)"""
+        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
+        if images.ndim == 4 and self.data_format == 'channels_first' and images.shape[1] == 3:
+            images = images.permute(0, 2, 3, 1)
+        if self.mode != 'test':
+            raise ValueError("test_images: the model was not built in test mode")
+        if images.ndim != 4 or not 1 <= images.shape[0] <= self.batch_size or tuple(images.shape[1:]) != tuple(self.images.shape[1:]):
+            raise ValueError(f"test_images: images must be [n, {', '.join(str(d) for d in self.images.shape[1:])}] with 1 <= n <= test_batch_size = "
+                             f"{self.batch_size}, not {tuple(images.shape)}")
+        n = images.shape[0]
+        self.images[:n].copy_(images)
+        return n
+
+    def test_images(self, images):
+        """images [n, H, W, 3] (or channels_first), n <= test_batch_size -> n [scores f32[K], bbox f32[K, 4], class_id i32[K]] triples (numpy)"""
+        n = self._stage_test_images(images)
+        self._forward_test()
+        t = self._tail_batched
+        if t is None:
+            t = self._tail_batched = self._make_tail()
+        self._launch_tail(t)
+        return t.read(n)
+
+    def test_one_image(self, images):
+        """one image [1, H, W, 3] (or channels_first) -> [scores, bbox, class_id]: test_images with one image (a model built without test_batch_size
+        has one image slot and refuses any other count)"""
+        return self.test_images(images)[0]
 
 
 def refinedet_anchors(input_size, device):
@@ -222,24 +279,11 @@ class RefineDetLoss:
         return self.loss_parts
 
 
-def refinedet_detect(arm_loc, arm_conf, odm_loc, odm_conf, anchors_yx, anchors_hw, score_thr, max_boxes, iou_thr):
-    """RefineDet.py:189-230 for one image: arm_loc / odm_loc [A, 4], arm_conf [A, 2], odm_conf [A, C] (last class = background)."""
-    conf, boxes, _, cand = ops.refinedet_decode(arm_loc, arm_conf, odm_loc, odm_conf, anchors_yx, anchors_hw, score_thr)
-    return _per_class_nms(conf, boxes, cand, odm_conf.shape[1] - 1, max_boxes, iou_thr)
-
-
 def fcos_detect(conf, reg, center, score_thr, max_boxes, iou_thr):
     """FCOS.py:197-265.  conf / reg / center: the five level tensors [H, W, C | 4 | 1] of one image; classes 0..C-2."""
     pconf, pbbox = ops.fcos_decode_candidates(conf, reg, center)
     cand = (pconf >= score_thr).to(torch.uint8)
     return _per_class_nms(pconf, pbbox, cand, pconf.shape[1] - 1, max_boxes, iou_thr)
-
-
-def yolov3_detect(preds, priors_flat, score_thr, max_boxes, iou_thr, decode_scale=(32., 32., 16.)):
-    """YOLOv3.py:320-368.  preds: three [H, W, P, C + 5] tensors (head 1 = coarsest); decode_scale as in the reference (sic)."""
-    conf, bbox = ops.yolov3_decode_candidates(preds, priors_flat, decode_scale)
-    cand = (conf >= score_thr).to(torch.uint8)
-    return _per_class_nms(conf, bbox, cand, conf.shape[1], max_boxes, iou_thr)
 
 
 def yolov2_detect(pred0, priors_flat, score_thr, max_boxes, iou_thr, stride=32.0):
@@ -262,9 +306,3 @@ class YOLOv2Loss:
         ops.yolov2_loss(pred.view(self.shape), self.priors_flat, stride, gt, self.scales, grad_scale, self.loss_parts, self.d_pred)
         return self.loss_parts
 
-
-def centernet_detect(keypoints, offset, size, score_thr, top_k, stride=4.0, workspace=None):
-    """CenterNet.py:159-185 (no NMS: 3x3 peak test + top-k)."""
-    H, W, C = keypoints.shape
-    ws = workspace if workspace is not None else ops.centernet_workspace(1, H, W, C, keypoints.device)
-    return ops.centernet_decode(keypoints, offset, size, stride, score_thr, top_k, ws)

@@ -9,7 +9,7 @@ Reference: /root/reference/RefineDet.py (class RefineDet320; `input_size` 320 or
   * ARM / TCB / ODM ...................... :387-415  (4 x [3x3(256) + BN + ReLU] + two 3x3 + BN outputs per level; TCB: 3x3 + BN + ReLU, 3x3 + BN,
                                                        + [4x4 / s2 transposed conv + BN] of the level above, ReLU)
   * loss, optimizer ...................... :160-187  (heads.RefineDetLoss: matching, NMS-mined ARM negatives, two-stage loss; Momentum 0.9)
-  * inference ............................ :189-230  (heads.refinedet_detect)
+  * inference ............................ :189-230  (heads.BatchedInference)
   * train / test / checkpoints ........... :583-617
 Layers by name (oracle/refinedet_net_ref.layer_specs' names), one flat f32 parameter buffer in TensorFlow's creation order.  The graph engine is
 centernet.py's (every activation owns its gradient buffer; a consumer writes it first or accumulates later), extended by the VGG convention of
@@ -28,7 +28,6 @@ import torch
 from . import heads, ops
 from ._lib import BF16
 from .base import DetectorBase
-from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -77,7 +76,7 @@ class _Act:
         self.g = None
 
 
-class RefineDet320(EvaluateMixin, F32Warmup, DetectorBase):
+class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
     # RefineDet320 / PFPNetR do not pass the bf16 gate (one head layer loses its direction); YOLOv2 does.  Round 4: their default is the f32 engine with
     # ODTK_F32X3 convolution descriptors (three bf16 MFMA products per f32 product): it passes the same gate at RANDOM INITIALISATION (minimum cosine 0.998 / 0.999
     # against the exact f32 engine) at 2.1x the exact engine's throughput (607 / 598 against 282 / 286 images/s)
@@ -588,41 +587,18 @@ class RefineDet320(EvaluateMixin, F32Warmup, DetectorBase):
         return self._data_loss + self.weight_decay * self.l2_sum      # RefineDet.py:180-184 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
-    NATIVE_TEST_IMAGES = True               # RefineDet320 and pfpnet.PFPNetR (inherited); yolov2.YOLOv2 and lhrcnn.LHRCNN reset it: their tails are not batched
-    _tail_batched = None
+    # (RefineDet320 and pfpnet.PFPNetR, which inherits; 6 375 / 16 320 anchors at 320 / 512: below the NMS capacity, no compaction.  yolov2.YOLOv2 and
+    # lhrcnn.LHRCNN put the single-image surface back: their tails are not batched)
+    def _forward_test(self):
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
 
-    def test_images(self, images):
-        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_refinedet_decode_batched -> odtk_nms_image_class
-        -> odtk_detection_pack -> one read-back (heads.BatchedTail; 6 375 / 16 320 anchors at 320 / 512: below the NMS capacity, no compaction).  Returns n
-        [scores, bbox, class_id] triples as test_one_image gives them."""
-        n = self._stage_test_images(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # the reference's quirk, as in test_one_image
-        N, A, nc = self.batch_size, self.A, self.num_classes - 1
-        t = self._tail_batched
-        if t is None:
-            t = self._tail_batched = heads.BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
-            # the decode's outputs ride on the tail object, as in ssd300.py / retinanet.py / yolov3.py (BatchedTail allocates only what the NMS and the pack write;
-            # tools/inference_bench.py reads t.conf / t.boxes / t.keep / t.cand of every native class)
-            t.conf = torch.zeros(N, A, nc, device=self.dev)
-            t.boxes = torch.zeros(N, A, 4, device=self.dev)
-            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
-            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
+    def _make_tail(self):
+        return heads.BatchedTail(self.batch_size, self.A, self.num_classes - 1, self.nms_max_boxes, self.dev)
+
+    def _launch_tail(self, t):
         ops.refinedet_decode_batched(self.arm_loc, self.arm_conf, self.odm_loc, self.odm_conf, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf,
                                      t.boxes, t.keep, t.cand)
-        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
-
-    def test_one_image(self, images):
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self.test_images(images)[0]
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
-        scores, bbox, cid = heads.refinedet_detect(self.arm_loc[0], self.arm_conf[0], self.odm_loc[0], self.odm_conf[0], self.anc[2], self.anc[3],
-                                                   self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold)
-        return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
+        t.launch_own(self.nms_iou_threshold)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
     # ------------------------------------------------------------------ the reference's variable names / tf.train.Saver files

@@ -7,7 +7,7 @@ Reference: /root/reference/RetinaNet.py -- the DETECTION graph (`is_pretraining:
                                            [BN-ReLU-1x1 f, BN-ReLU-3x3 f (stride), BN-ReLU-1x1 4f] + [BN-ReLU-3x3 4f (stride)] shortcut
   * pyramid, subnets ..................... :138-155, :287-319 (bilinear top-down path, the SUM is handed down; subnets not shared)
   * loss, optimizer ...................... :172-217  (odtk_retina_match / odtk_retina_loss; Momentum 0.9; L2 over all variables)
-  * inference ............................ :218-256  (heads.retina_detect)
+  * inference ............................ :218-256  (heads.BatchedInference)
   * train / test / checkpoints ........... :488-535
 The classification pre-training graph (`is_pretraining: True`, :61-99, :120-135, :476-531, :548-551) is built behind the same class:
   * the backbone alone (l0 .. l64), the LAST unit's sum (no batch norm / ReLU after it) -> global average pool -> softmax cross-entropy
@@ -32,7 +32,6 @@ import torch
 from . import heads, ops
 from ._lib import BF16
 from .base import DetectorBase, _Act
-from .voc_eval import EvaluateMixin
 
 MEAN_RGB = (123.68, 116.779, 103.979)
 FILTERS = (7, 14, 28, 56)                                     # RetinaNet.py:27 (sic)
@@ -83,7 +82,7 @@ def level_priors(size):
     return out
 
 
-class RetinaNet(EvaluateMixin, DetectorBase):
+class RetinaNet(heads.BatchedInference, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         self.is_pretraining = bool(config.get('is_pretraining'))
@@ -428,27 +427,22 @@ class RetinaNet(EvaluateMixin, DetectorBase):
         return self.loss_parts.sum() / self.batch_size + self.weight_decay * self.l2_sum          # RetinaNet.py:205-213
 
     # ------------------------------------------------------------------ public: inference
-    NATIVE_TEST_IMAGES = True
-    _tail_batched = None
-
     def test_images(self, images):
-        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_retina_decode_batched -> (more anchors than the
-        NMS takes per problem: odtk_compact_rows + odtk_gather_rows, the place torch.nonzero holds in the single-image path) -> odtk_nms_image_class ->
-        odtk_detection_pack -> one read-back.  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
+        """heads.BatchedInference.test_images (with more anchors than the NMS takes per problem the tail compacts the candidate rows first: odtk_compact_rows +
+        odtk_gather_rows); a pre-training model returns the predicted classes instead"""
         if self.is_pretraining:
             return self._test_pretraining_images(images)
-        n = self._stage_test_images(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        N, A, nc = self.batch_size, self.pconf.shape[1], self.num_classes - 1
-        t = self._tail_batched
-        if t is None:
-            t = self._tail_batched = heads.BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
-            t.conf = torch.zeros(N, A, nc, device=self.dev)
-            t.boxes = torch.zeros(N, A, 4, device=self.dev)
-            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
-            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
+        return super().test_images(images)
+
+    def _forward_test(self):
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
+
+    def _make_tail(self):
+        return heads.BatchedTail(self.batch_size, self.pconf.shape[1], self.num_classes - 1, self.nms_max_boxes, self.dev)
+
+    def _launch_tail(self, t):
         ops.retina_decode_batched(self.pconf, self.pbox, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
-        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
+        t.launch_own(self.nms_iou_threshold)
 
     def evaluate(self, num_images=None, generator=None, **kw):
         """detection graph: VOC mAP (voc_eval.EvaluateMixin.evaluate).  Pre-training graph: held-out accuracy, see _evaluate_pretraining
@@ -456,19 +450,6 @@ class RetinaNet(EvaluateMixin, DetectorBase):
         if self.is_pretraining:
             return self._evaluate_pretraining(num_images, generator, **kw)
         return super().evaluate(num_images, generator, **kw)
-
-    def test_one_image(self, images):
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self.test_images(images)[0]
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        scores, bbox, cid = heads.retina_detect(self.pconf[0], self.pbox[0], self.anc[2], self.anc[3], self.nms_score_threshold,
-                                                self.nms_max_boxes, self.nms_iou_threshold)
-        return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
     def export_tf_variables(self):
@@ -680,20 +661,12 @@ class RetinaNet(EvaluateMixin, DetectorBase):
         """test_images of a test-mode pre-training model: n <= test_batch_size images in one forward pass at N = test_batch_size -> the predicted
         classes, int64 [n] (moving statistics 0 / 1 as in the reference: see _evaluate_pretraining for held-out accuracy)"""
         n = self._stage_test_images(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        self._forward_test()
         return self.pred[:n].cpu().numpy().astype(np.int64)
 
     def _test_one_pretraining_image(self, images):
         """RetinaNet.py:501-503: the predicted class, int64 [1] (the fed tensor bypasses the mean subtraction unless test_subtract_mean)"""
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self._test_pretraining_images(images)
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        return self.pred.cpu().numpy().astype(np.int64)
+        return self._test_pretraining_images(images)
 
     def export_pretraining_tf_variables(self):
         """what the pre-training `tf.train.Saver(tf.trainable_variables('feature_extractor'))` (RetinaNet.py:548-551) writes: the kernels, biases,

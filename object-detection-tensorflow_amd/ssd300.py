@@ -33,7 +33,7 @@ import torch
 from . import _lib, ops
 from ._lib import BF16, F32, F32X3
 from .base import DetectorBase
-from .voc_eval import EvaluateMixin
+from .heads import BatchedInference, BatchedTail
 from .warmup import F32Warmup
 
 INPUT_SIZE = 300
@@ -145,7 +145,7 @@ class _Conv:
         self.bn, self.relu = bn, relu
 
 
-class SSD300(EvaluateMixin, F32Warmup, DetectorBase):
+class SSD300(BatchedInference, F32Warmup, DetectorBase):
     # the variant: SSD512 (ssd512.py) overrides these
     INPUT_SIZE = INPUT_SIZE
     FEATURE_SIZES = FEATURE_SIZES
@@ -483,11 +483,6 @@ class SSD300(EvaluateMixin, F32Warmup, DetectorBase):
         self.loss_parts = torch.zeros(N, 4, device=dev)
         self.data_loss = torch.zeros(1, device=dev)
         self.loss_ring = torch.zeros(8, device=dev)
-        nc = self.num_classes - 1
-        self.d_conf = torch.zeros(A, nc, device=dev)
-        self.d_boxes = torch.zeros(A, 4, device=dev)
-        self.d_keep = torch.zeros(A, dtype=torch.uint8, device=dev)
-        self.d_cand = torch.zeros(A, nc, dtype=torch.uint8, device=dev)
         self.refresh_wt()
 
     def _refresh_operand_copies(self):
@@ -1146,55 +1141,17 @@ class SSD300(EvaluateMixin, F32Warmup, DetectorBase):
         return np.mean(mean_loss)
 
     # ------------------------------------------------------------------ public: inference
-    NATIVE_TEST_IMAGES = True
-    _tail_batched = None
-
-    def test_images(self, images):
-        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail: odtk_ssd_decode_batched -> odtk_nms_image_class
-        (N x classes problems) -> odtk_detection_pack -> one read-back.  Returns n [scores, bbox, class_id] triples as test_one_image gives them."""
-        n = self._stage_test_images(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        N, A, nc = self.batch_size, self.NUM_PRIORS, self.num_classes - 1
-        t = self._tail_batched
-        if t is None:
-            from .heads import BatchedTail
-            t = self._tail_batched = BatchedTail(N, A, nc, self.nms_max_boxes, self.dev)
-            t.conf = torch.zeros(N, A, nc, device=self.dev)
-            t.boxes = torch.zeros(N, A, 4, device=self.dev)
-            t.keep = torch.zeros(N, A, dtype=torch.uint8, device=self.dev)
-            t.cand = torch.zeros(N, A, nc, dtype=torch.uint8, device=self.dev)
-        ops.ssd_decode_batched(self.pred, self.num_classes, self.pri[2], self.pri[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
-        return t(t.conf, t.boxes, t.cand, self.nms_iou_threshold, n)
-
-    def test_one_image(self, images):
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self.test_images(images)[0]
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == (1, self.INPUT_SIZE, self.INPUT_SIZE, 3)
-        self.images.copy_(images)
+    def _forward_test(self):
         # Reference quirk, reproduced by default: test mode re-binds self.images to `placeholder - mean`
         # and feeds THAT tensor (SSD300.py:65-66,487), so fed pixels bypass the mean subtraction.
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        nc = self.num_classes - 1
-        pri = self.pri
-        ops.ssd_decode(self.pred[0], self.num_classes, pri[2], pri[3], self.nms_score_threshold, self.d_conf,
-                       self.d_boxes, self.d_keep, self.d_cand)
-        cap = max(int(self.nms_max_boxes), 1)
-        out_idx = torch.zeros(nc, cap, dtype=torch.int32, device=self.dev)
-        out_cnt = torch.zeros(nc, dtype=torch.int32, device=self.dev)
-        ops.nms_batched(self.d_boxes, 0, self.d_conf, 1, nc, self.d_cand, 1, nc, 1, self.NUM_PRIORS, nc, None, 0,
-                        int(self.nms_max_boxes), self.nms_iou_threshold, out_idx, cap, out_cnt)
-        cnt = out_cnt.cpu().tolist()
-        idx = out_idx.cpu()
-        conf, boxes = self.d_conf.cpu(), self.d_boxes.cpu()
-        scores, bbox, cid = [], [], []
-        for c in range(nc):                           # ascending class id, NMS pick order inside
-            ids = idx[c, : cnt[c]].long()
-            scores.append(conf[ids, c]); bbox.append(boxes[ids])
-            cid.append(torch.full((cnt[c],), c, dtype=torch.int32))
-        return [torch.cat(scores).numpy(), torch.cat(bbox, 0).numpy().reshape(-1, 4), torch.cat(cid).numpy()]
+
+    def _make_tail(self):
+        return BatchedTail(self.batch_size, self.NUM_PRIORS, self.num_classes - 1, self.nms_max_boxes, self.dev)
+
+    def _launch_tail(self, t):
+        ops.ssd_decode_batched(self.pred, self.num_classes, self.pri[2], self.pri[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)
+        t.launch_own(self.nms_iou_threshold)
 
     # ------------------------------------------------------------------ checkpoints
     def tf_variable_map(self):

@@ -389,11 +389,11 @@ class EvaluateMixin:
     copy per batch_size (built with test_batch_size = B) in `self._eval_models`; each copy holds its own weights and activation buffers at N = B on the
     device until the entry is deleted (`del model._eval_models[B]`), so evaluate with ONE batch size per run rather than sweeping them.
 
-    `test_images(images)` here is the fallback form: a LOOP over `test_one_image`, NOT batched (FCOS, YOLOv2, Light-Head R-CNN).  Seven classes override
-    it with one forward pass at N = test_batch_size and a batched tail: SSD300, SSD512, YOLOv3, RetinaNet, RefineDet320 and PFPNetR (heads.BatchedTail)
-    and CenterNet (heads.CenterNetBatched)."""
+    `test_images(images)` here is the fallback form: a LOOP over `test_one_image`, NOT batched (FCOS, YOLOv2, Light-Head R-CNN).  The other seven
+    classes -- SSD300, SSD512, YOLOv3, RetinaNet, CenterNet, RefineDet320, PFPNetR -- take both from heads.BatchedInference: one forward pass at
+    N = test_batch_size and a batched tail, with test_one_image as its one-image case."""
 
-    NATIVE_TEST_IMAGES = False               # True in the classes whose test_images is one batched forward + tail
+    NATIVE_TEST_IMAGES = False               # True in heads.BatchedInference
 
     def test_images(self, images):
         """images [n, H, W, 3] (or channels_first, as test_one_image accepts it) -> list of n [scores, bbox, class_id] triples, each exactly what
@@ -402,28 +402,6 @@ class EvaluateMixin:
         if images.ndim != 4 or images.shape[0] < 1:
             raise ValueError(f"test_images: images must be [n, H, W, 3] (or channels_first) with n >= 1, not {tuple(images.shape)}")
         return [self.test_one_image(images[b: b + 1]) for b in range(images.shape[0])]
-
-    def _stage_test_images(self, images):
-        """native classes: the n <= test_batch_size images into the first n slots of self.images (the tail slots keep what they held: computed, discarded)"""
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if images.ndim == 4 and self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        if self.mode != 'test':
-            raise ValueError("test_images: the model was not built in test mode")
-        if images.ndim != 4 or not 1 <= images.shape[0] <= self.batch_size or tuple(images.shape[1:]) != tuple(self.images.shape[1:]):
-            raise ValueError(f"test_images: images must be [n, {', '.join(str(d) for d in self.images.shape[1:])}] with 1 <= n <= test_batch_size = "
-                             f"{self.batch_size}, not {tuple(images.shape)}")
-        n = images.shape[0]
-        self.images[:n].copy_(images)
-        return n
-
-    @staticmethod
-    def _test_batch_size(config):
-        """config['test_batch_size']: optional, an integer >= 1 (default 1), read in test mode only: the number of image slots of the test-mode buffers"""
-        b = config.get('test_batch_size', 1)
-        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
-            raise ValueError(f"test_batch_size must be an integer >= 1, not {b!r}")
-        return int(b)
 
     def evaluate(self, num_images=None, generator=None, **kw):
         if getattr(self, 'is_pretraining', False):

@@ -8,7 +8,7 @@ Reference: /root/reference/YOLOv3.py
                                                 (+ leaky_relu 0.1), INCLUDING the three prediction convs; lateral convs without activation;
                                                 heads built with 1024 / 256 / 128 filters on block5 / block4 / block3
   * loss, optimizer ........................... :96-318    (odtk_yolov3_loss; .5 * mean + wd * l2; Momentum 0.9; BN update ops)
-  * inference ................................. :320-368    (heads.yolov3_detect)
+  * inference ................................. :320-368    (heads.BatchedInference)
   * train_one_epoch / test_one_image / save_weight / load_weight ... :437-482
 Every convolution, batch norm, residual sum, up-sampling and the box side run in libodtk (no torch compute, no CPU
 fallback); this file owns the buffers, the launch order and the gradient bookkeeping:
@@ -32,7 +32,6 @@ import torch
 from . import heads, ops
 from ._lib import BF16
 from .base import DetectorBase, _Act
-from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)                                       # YOLOv3.py:65
@@ -42,7 +41,7 @@ STRIDE = (8., 16., 32.)                                                     # :3
 LEAKY = 2                                                                   # odtk_bn_fwd activation code
 
 
-class YOLOv3(EvaluateMixin, F32Warmup, DetectorBase):
+class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         self._prologue(config, data_provider, native_test_batch=True, num_val_optional=True)      # (this class reads num_val only with a val_generator)
@@ -296,41 +295,22 @@ class YOLOv3(EvaluateMixin, F32Warmup, DetectorBase):
         return 0.5 * self.loss_parts[:, 4].mean() + self.weight_decay * self.l2_sum        # YOLOv3.py:311-315 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
-    NATIVE_TEST_IMAGES = True
-    _tail_batched = None
+    def _forward_test(self):
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
 
-    def test_images(self, images):
-        """n <= test_batch_size images in ONE forward pass at N = test_batch_size, then the batched tail (heads.BatchedTail).  The decode is a LOOP of the
-        existing launch, odtk_yolov3_decode_candidates, one per image slot into [N, L, C] / [N, L, 4]: that entry point takes the three level tensors of an
-        image as a pointer table, a batched form would need a table per image, and the loop costs the host's enqueue time, measured 0.5 ms for 32 images (15 us per image, DESIGN.md *Evaluation*) beside a forward pass of 26 ms;
-        threshold, NMS (N x classes problems), pack and read-back are batched."""
-        n = self._stage_test_images(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        N, C_ = self.batch_size, self.num_classes
+    def _make_tail(self):
         L = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in self.preds)
-        t = self._tail_batched
-        if t is None:
-            t = self._tail_batched = heads.BatchedTail(N, L, C_, self.nms_max_boxes, self.dev)
-            t.conf = torch.zeros(N, L, C_, device=self.dev)
-            t.boxes = torch.zeros(N, L, 4, device=self.dev)
-            t.cand = torch.zeros(N, L, C_, dtype=torch.bool, device=self.dev)
-        for b in range(N):
+        return heads.BatchedTail(self.batch_size, L, self.num_classes, self.nms_max_boxes, self.dev, bool_cand=True)
+
+    def _launch_tail(self, t):
+        """The decode is a LOOP of the existing launch, odtk_yolov3_decode_candidates, one per image slot into [N, L, C] / [N, L, 4]: that entry point takes the
+        three level tensors of an image as a pointer table, a batched form would need a table per image, and the loop costs the host's enqueue time, measured
+        0.5 ms for 32 images (15 us per image, DESIGN.md *Evaluation*) beside a forward pass of 26 ms; threshold, NMS (N x classes problems), pack and
+        read-back are batched."""
+        for b in range(self.batch_size):
             ops.yolov3_decode_candidates([p[b] for p in self.preds], self.priors_flat, (STRIDE[2], STRIDE[2], STRIDE[1]), out=(t.conf[b], t.boxes[b]))
         torch.ge(t.conf, self.nms_score_threshold, out=t.cand)
-        return t(t.conf, t.boxes, t.cand.view(torch.uint8), self.nms_iou_threshold, n)
-
-    def test_one_image(self, images):
-        if self.batch_size > 1:                       # built with test_batch_size > 1: the batched path with one image
-            return self.test_images(images)[0]
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
-        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
-        scores, bbox, cid = heads.yolov3_detect([p[0] for p in self.preds], self.priors_flat, self.nms_score_threshold, self.nms_max_boxes,
-                                                self.nms_iou_threshold, decode_scale=(STRIDE[2], STRIDE[2], STRIDE[1]))
-        return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
+        t.launch_own(self.nms_iou_threshold)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
     def export_tf_variables(self):

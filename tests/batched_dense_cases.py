@@ -3,6 +3,8 @@ kernels run from source under the emulation): odtk_centernet_decode_batched and 
 import numpy as np
 import torch
 
+from single_image_tail import centernet_detect, refinedet_detect
+
 STRIDE = 4.0
 THR = 0.3             # score threshold of the CenterNet cases: sigmoid(-2) = 0.12 < THR < sigmoid(1) = 0.73
 
@@ -84,7 +86,7 @@ def check_centernet_read_back(dev):
     part = tail(kp, off, size, THR, STRIDE, n_images=2)
     assert len(got) == 3 and len(part) == 2 and [len(d[0]) for d in got] == [0, top_k, 7]
     for n in range(3):
-        s, b, c = heads.centernet_detect(kp[n], off[n], size[n], THR, top_k, STRIDE)
+        s, b, c = centernet_detect(kp[n], off[n], size[n], THR, top_k, STRIDE)
         assert _same(got[n], [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()]), n
         assert n == 2 or _same(part[n], got[n])
     return tail, kp, off, size
@@ -118,5 +120,5 @@ def check_refinedet(N, A, C, dev):
     assert not tail.compact
     got = tail(conf, boxes, cand, iou)
     for n in range(N):
-        s, b, c = heads.refinedet_detect(arm_loc[n], arm_conf[n], odm_loc[n], odm_conf[n], yx, hw, thr, max_boxes, iou)
+        s, b, c = refinedet_detect(arm_loc[n], arm_conf[n], odm_loc[n], odm_conf[n], yx, hw, thr, max_boxes, iou)
         assert s.numel() > 0 and _same(got[n], [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()]), n

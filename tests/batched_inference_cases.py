@@ -9,24 +9,6 @@ N_IMAGES = 5
 SHAPES = {'ssd': (8828, 21), 'retina': (40000, 21)}          # (rows per image, classes incl. background); 40 000 > the NMS capacity of 32 768 rows
 
 
-def nms_image_class_via(nms_batched):
-    """odtk_nms_image_class's operand addressing (include/odtk.h) around a stand-in for odtk_nms_batched: one call per image, its classes as the problems"""
-    def nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, score_estride, valid, valid_istride, valid_cstride, valid_estride,
-                        valid_value, n, n_dev, N, num_classes, max_out, iou_thr, out_idx, cap, out_cnt):
-        bx, sc = boxes.reshape(-1), scores.reshape(-1)
-        vd = valid.reshape(-1) if valid is not None else None
-        for img in range(N):
-            ni = n if n_dev is None else min(n, max(int(n_dev[img]), 0))
-            if ni == 0:
-                out_cnt[img] = 0
-                continue
-            per = (ni - 1) * score_estride + (num_classes - 1) * score_cstride + 1
-            nms_batched(bx[img * box_istride: img * box_istride + 4 * ni], 0, sc[img * score_istride: img * score_istride + per], score_cstride, score_estride,
-                        None if vd is None else vd[img * valid_istride: img * valid_istride + (ni - 1) * valid_estride + (num_classes - 1) * valid_cstride + 1],
-                        valid_cstride, valid_estride, valid_value, ni, num_classes, None, 0, int(max_out), float(iou_thr), out_idx[img], cap, out_cnt[img])
-    return nms_image_class
-
-
 def make_heads(kind, seed):
     """seeded head tensors of N_IMAGES images with distinct scores: background wins everywhere except on 400 chosen rows per image, which carry one of the
     image's 3 + n foreground classes well above the threshold; the LAST image has no such row (zero detections); classes >= 8 never occur"""
@@ -56,7 +38,8 @@ def _priors(kind, dev):
 
 def single_image_tail(kind, logits, box, yx, hw, n, dev):
     """the existing single-image tail on image n alone: odtk_ssd_decode / odtk_retina_decode -> odtk_nms_batched -> host gather"""
-    from odtk import heads, ops
+    from odtk import ops
+    from single_image_tail import retina_detect
     A, C = SHAPES[kind]
     nc = C - 1
     if kind == 'ssd':
@@ -66,7 +49,7 @@ def single_image_tail(kind, logits, box, yx, hw, n, dev):
         ops.ssd_decode(pred0, C, yx, hw, SCORE_THR, conf, boxes, keep, cand)
         cap = NMS_MAX_BOXES
         out_idx = torch.zeros(nc, cap, dtype=torch.int32, device=dev); out_cnt = torch.zeros(nc, dtype=torch.int32, device=dev)
-        ops.nms_batched(boxes, 0, conf, 1, nc, cand, 1, nc, 1, A, nc, None, 0, NMS_MAX_BOXES, IOU_THR, out_idx, cap, out_cnt)      # (SSD300.test_one_image)
+        ops.nms_batched(boxes, 0, conf, 1, nc, cand, 1, nc, 1, A, nc, None, 0, NMS_MAX_BOXES, IOU_THR, out_idx, cap, out_cnt)
         cnt, idx, conf_h, boxes_h = out_cnt.cpu().tolist(), out_idx.cpu(), conf.cpu(), boxes.cpu()
         s, b, c = [], [], []
         for k in range(nc):
@@ -75,7 +58,7 @@ def single_image_tail(kind, logits, box, yx, hw, n, dev):
         return [torch.cat(s).numpy(), torch.cat(b, 0).numpy().reshape(-1, 4), torch.cat(c).numpy()], (conf, boxes, keep, cand)
     pconf, pbox = logits[n].contiguous().to(dev), box[n].contiguous().to(dev)
     dec = ops.retina_decode(pconf, pbox, yx, hw, SCORE_THR)
-    s, b, c = heads.retina_detect(pconf, pbox, yx, hw, SCORE_THR, NMS_MAX_BOXES, IOU_THR)                   # (RetinaNet.test_one_image: torch.nonzero above 32 768 rows)
+    s, b, c = retina_detect(pconf, pbox, yx, hw, SCORE_THR, NMS_MAX_BOXES, IOU_THR)                         # (torch.nonzero above 32 768 rows)
     return [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()], dec
 
 
@@ -119,6 +102,42 @@ def check_tail(kind, dev, seed=11):
         for name, a, b in zip(('scores', 'bbox', 'class_id'), got[n], want):
             assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), (kind, n, name, a.shape, b.shape)
     return per
+
+
+def check_default_model(m, imgs, thresholds, cap):
+    """a model built WITHOUT test_batch_size (one image slot), two pictures x two thresholds: test_one_image == (every array, dtype and shape) the single-image
+    tail (tests/single_image_tail.py) on the head tensors that very forward pass left in the model, and == test_images of that picture [0]; not vacuous:
+    detections, and somewhere a class (CenterNet: an image) that fills its `cap` = nms_max_boxes (top_k_results_output)"""
+    import single_image_tail as ST
+    assert m.batch_size == 1 and m.images.shape[0] == 1 and 'test_batch_size' not in m.config and m.NATIVE_TEST_IMAGES and len(thresholds) == 2
+    key = 'nms_score_threshold' if hasattr(m, 'nms_score_threshold') else 'score_threshold'
+    same = lambda a, b: len(a) == 3 and len(b) == 3 and all(x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
+    old, counts, fullest = getattr(m, key), [], 0
+    try:
+        for thr in thresholds:
+            setattr(m, key, thr)
+            for n in range(2):
+                x = np.ascontiguousarray(imgs[n: n + 1])
+                got = m.test_one_image(x)
+                want = ST.of_model(m)
+                assert same(got, want), (thr, n, [a.shape for a in got], [a.shape for a in want])
+                again = m.test_images(x)
+                assert len(again) == 1 and same(got, again[0]), (thr, n)
+                counts.append(len(got[0]))
+                fullest = max(fullest, len(got[0]) if key == 'score_threshold' else int(np.bincount(got[2], minlength=1).max(initial=0)))
+    finally:
+        setattr(m, key, old)
+    print(f'{type(m).__name__}: detections per (threshold, picture) {counts}, fullest class {fullest} of {cap}')
+    assert sum(counts) > 0 and fullest == cap, (counts, fullest, cap)
+    for bad in (np.concatenate([imgs[:1], imgs[:1]]), imgs[:1, :-1]):              # one slot: two images, or another size, are refused by the staging
+        for f in (m.test_one_image, m.test_images):
+            try:
+                f(bad)
+            except ValueError as e:
+                assert 'test_images' in str(e)
+            else:
+                raise AssertionError('a bad input was accepted')
+    return counts
 
 
 def check_compaction(dev):

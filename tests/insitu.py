@@ -55,7 +55,9 @@ ON_CPU = {'ssd_loss', 'yolov3_loss', 'yolov2_loss', 'retina_loss', 'fcos_loss', 
 # real kernels' indices are compared bit for bit by the kernel-level tests), workspaces, scratch selection, constant tables
 PASS = {'conv2d_fwd_pool2x2_fused', 'conv2d_x3_supported', 'conv2d_relu_bits_supported', 'ssd_match', 'softmax_ce_const', 'retina_match', 'nms_batched', 'scratch_slot', 'ssd_priors', 'retina_anchors', 'gn_workspace', 'fcos_workspace',
         'yolov3_workspace', 'retina_match_workspace', 'centernet_workspace', 'yolov3_decode_candidates', 'fcos_decode_candidates', 'retina_decode',
-        'refinedet_decode', 'centernet_decode', 'yolov2_decode_candidates', 'lhrcnn_match', 'lhrcnn_rpn_decode', 'lhrcnn_gather_rois', 'lhrcnn_rcnn_decode'}
+        'refinedet_decode', 'centernet_decode', 'yolov2_decode_candidates', 'lhrcnn_match', 'lhrcnn_rpn_decode', 'lhrcnn_gather_rois', 'lhrcnn_rcnn_decode',
+        'ssd_decode', 'ssd_decode_batched', 'retina_decode_batched', 'refinedet_decode_batched', 'centernet_decode_batched', 'centernet_decode_workspace',
+        'nms_image_class', 'compact_rows', 'gather_rows', 'detection_pack'}
 WHOLE_STORAGE_MAX = 1 << 30
 BN_MOM_ = 0.99
 

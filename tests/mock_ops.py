@@ -391,11 +391,15 @@ def nms_batched(boxes, box_stride, scores, score_bstride, score_estride, valid, 
         out_cnt[b] = k
 
 
-def yolov3_decode_candidates(preds, priors_flat, decode_scale):
+def yolov3_decode_candidates(preds, priors_flat, decode_scale, out=None):
     from oracle import yolov3_ref as YR
     assert [float(v) for v in decode_scale] == [32., 32., 16.]
     pri = [[[priors_flat[(l * 3 + a) * 2] * YR.STRIDE[l], priors_flat[(l * 3 + a) * 2 + 1] * YR.STRIDE[l]] for a in range(3)] for l in range(3)]
-    return YR.decode_candidates([p.float() for p in preds], num_classes=preds[0].shape[-1] - 5, priors_px=pri)
+    conf, bbox = YR.decode_candidates([p.float() for p in preds], num_classes=preds[0].shape[-1] - 5, priors_px=pri)
+    if out is not None:
+        out[0].copy_(conf); out[1].copy_(bbox)
+        return out
+    return conf, bbox
 
 
 def fcos_decode_candidates(conf, reg, center):
@@ -407,6 +411,95 @@ def retina_decode(pconf, pbox, yx, hw, thr):
     from oracle import retinanet_ref as RR
     conf, boxes, keep, cand = RR.decode_candidates(pbox[:, :2], pbox[:, 2:], pconf, (None, None, yx, hw), thr, num_classes=pconf.shape[1])
     return conf.contiguous(), boxes.contiguous(), keep.to(torch.uint8), cand.to(torch.uint8)
+
+
+def ssd_decode(pred0, Cn, yx, hw, thr, conf, boxes, keep, cand):
+    p = torch.softmax(pred0[..., :Cn], -1)
+    kp = p.argmax(-1) < Cn - 1
+    conf.copy_(p[..., : Cn - 1]); keep.copy_(kp.to(torch.uint8))
+    cand.copy_((kp[..., None] & (p[..., : Cn - 1] >= thr)).to(torch.uint8))
+    z = pred0[..., Cn: Cn + 4]
+    cy, cx = z[..., 0] * hw[:, 0] + yx[:, 0], z[..., 1] * hw[:, 1] + yx[:, 1]
+    h, w = hw[:, 0] * torch.exp(z[..., 2]), hw[:, 1] * torch.exp(z[..., 3])
+    boxes.copy_(torch.stack([cy - h / 2, cx - w / 2, cy + h / 2, cx + w / 2], -1))
+
+
+# ---- the batched inference tail: per image, the single-image stand-ins above; compaction and pack in plain torch
+def ssd_decode_batched(pred, Cn, yx, hw, thr, conf, boxes, keep, cand):
+    for n in range(pred.shape[0]):
+        ssd_decode(pred[n], Cn, yx, hw, thr, conf[n], boxes[n], keep[n], cand[n])
+
+
+def retina_decode_batched(pconf, pbox, yx, hw, thr, conf, boxes, keep, cand):
+    for n in range(pconf.shape[0]):
+        for dst, src in zip((conf[n], boxes[n], keep[n], cand[n]), retina_decode(pconf[n], pbox[n], yx, hw, thr)):
+            dst.copy_(src)
+
+
+def refinedet_decode_batched(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr, conf, boxes, keep, cand):
+    for n in range(odm_conf.shape[0]):
+        for dst, src in zip((conf[n], boxes[n], keep[n], cand[n]), refinedet_decode(arm_loc[n], arm_conf[n], odm_loc[n], odm_conf[n], yx, hw, thr)):
+            dst.copy_(src)
+
+
+def centernet_decode_workspace(N, H, W, device):
+    return torch.zeros(4, dtype=torch.uint8)
+
+
+def centernet_decode_batched(keypoints, offset, size, stride, score_threshold, top_k, scores, bbox, class_id, counts, ws):
+    for n in range(keypoints.shape[0]):
+        s, b, c = centernet_decode(keypoints[n], offset[n], size[n], stride, score_threshold, top_k, None)
+        k = len(s)
+        scores[n, :k] = s; bbox[n, :k] = b.reshape(-1, 4); class_id[n, :k] = c.to(torch.int32); counts[n] = k
+
+
+def nms_image_class_via(nms_batched):
+    """odtk_nms_image_class's operand addressing (include/odtk.h) around a stand-in for odtk_nms_batched: one call per image, its classes as the problems"""
+    def nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, score_estride, valid, valid_istride, valid_cstride, valid_estride,
+                        valid_value, n, n_dev, N, num_classes, max_out, iou_thr, out_idx, cap, out_cnt):
+        bx, sc = boxes.reshape(-1), scores.reshape(-1)
+        vd = valid.reshape(-1) if valid is not None else None
+        for img in range(N):
+            ni = n if n_dev is None else min(n, max(int(n_dev[img]), 0))
+            if ni == 0:
+                out_cnt[img] = 0
+                continue
+            per = (ni - 1) * score_estride + (num_classes - 1) * score_cstride + 1
+            nms_batched(bx[img * box_istride: img * box_istride + 4 * ni], 0, sc[img * score_istride: img * score_istride + per], score_cstride, score_estride,
+                        None if vd is None else vd[img * valid_istride: img * valid_istride + (ni - 1) * valid_estride + (num_classes - 1) * valid_cstride + 1],
+                        valid_cstride, valid_estride, valid_value, ni, num_classes, None, 0, int(max_out), float(iou_thr), out_idx[img], cap, out_cnt[img])
+    return nms_image_class
+
+
+nms_image_class = nms_image_class_via(nms_batched)
+
+
+def compact_rows(cand, num_classes, cap_rows, rows, counts):
+    for n in range(cand.shape[0]):
+        r = torch.nonzero(cand[n, :, :num_classes].any(1)).flatten()
+        k = min(r.numel(), cap_rows)
+        rows[n, :k] = r[:k].to(rows.dtype)
+        counts[n] = r.numel()                                  # the TRUE count, also above the capacity
+
+
+def gather_rows(rows, counts, num_classes, conf, boxes, cand, conf_out, boxes_out, cand_out):
+    for n in range(rows.shape[0]):
+        r = rows[n, : min(int(counts[n]), rows.shape[1])].long()
+        k = r.numel()
+        conf_out[n, :k] = conf[n, r, :num_classes]; boxes_out[n, :k] = boxes[n, r]; cand_out[n, :k] = cand[n, r, :num_classes]
+
+
+def detection_pack(nms_idx, nms_cnt, conf, boxes, counts, offsets, scores, bbox, class_id):
+    N, nc, _ = nms_idx.shape
+    k = 0
+    offsets[0] = 0
+    for i in range(N):
+        for c in range(nc):
+            for j in range(int(nms_cnt[i, c])):
+                r = int(nms_idx[i, c, j])
+                scores[k] = conf[i, r, c]; bbox[k] = boxes[i, r]; class_id[k] = c
+                k += 1
+        counts[i] = k - int(offsets[i]); offsets[i + 1] = k
 
 
 # ---- SSD300-specific launches
@@ -670,7 +763,7 @@ def installed():
     """swap the launching functions of odtk.ops for the ones above (and back)"""
     import odtk  # noqa: F401
     from odtk import ops
-    names = [n for n, v in globals().items() if callable(v) and not n.startswith('_') and n not in ('installed', 'contextlib') and hasattr(ops, n)]
+    names = [n for n, v in globals().items() if callable(v) and not n.startswith('_') and n not in ('installed', 'contextlib') and hasattr(ops, n)]      # (nms_image_class_via: not in ops)
     old = {n: getattr(ops, n) for n in names}
     from odtk import _lib
 

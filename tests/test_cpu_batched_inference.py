@@ -14,6 +14,7 @@ import torch
 
 import batched_inference_cases as BC
 import hip_cpu_backend as HC
+import mock_ops
 
 
 @contextlib.contextmanager
@@ -31,7 +32,7 @@ def emulated():
         with HC.installed() as names:
             assert 'odtk_detection_pack' in names and 'odtk_compact_rows' in names
             old = ops.nms_image_class
-            ops.nms_image_class = BC.nms_image_class_via(ops.nms_batched)
+            ops.nms_image_class = mock_ops.nms_image_class_via(ops.nms_batched)
             try:
                 yield
             finally:
@@ -76,45 +77,13 @@ def test_emulated_pack_order_and_scan():
 
 
 # ---------------------------------------------------------------- host logic over mocked launches
-def _ssd_decode_batched(pred, Cn, yx, hw, thr, conf, boxes, keep, cand):
-    p = torch.softmax(pred[..., :Cn], -1)
-    kp = p.argmax(-1) < Cn - 1
-    conf.copy_(p[..., : Cn - 1]); keep.copy_(kp.to(torch.uint8))
-    cand.copy_((kp[..., None] & (p[..., : Cn - 1] >= thr)).to(torch.uint8))
-    z = pred[..., Cn: Cn + 4]
-    cy, cx = z[..., 0] * hw[:, 0] + yx[:, 0], z[..., 1] * hw[:, 1] + yx[:, 1]
-    h, w = hw[:, 0] * torch.exp(z[..., 2]), hw[:, 1] * torch.exp(z[..., 3])
-    boxes.copy_(torch.stack([cy - h / 2, cx - w / 2, cy + h / 2, cx + w / 2], -1))
-
-
-def _detection_pack(nms_idx, nms_cnt, conf, boxes, counts, offsets, scores, bbox, class_id):
-    N, nc, _ = nms_idx.shape
-    k = 0
-    offsets[0] = 0
-    for i in range(N):
-        for c in range(nc):
-            for j in range(int(nms_cnt[i, c])):
-                r = int(nms_idx[i, c, j])
-                scores[k] = conf[i, r, c]; bbox[k] = boxes[i, r]; class_id[k] = c
-                k += 1
-        counts[i] = k - int(offsets[i]); offsets[i + 1] = k
-
-
-@contextlib.contextmanager
 def mocked():
-    import mock_ops
-    from odtk import ops
-    with mock_ops.installed():
-        old = ops.ssd_decode_batched, ops.nms_image_class, ops.detection_pack
-        ops.ssd_decode_batched, ops.detection_pack = _ssd_decode_batched, _detection_pack
-        ops.nms_image_class = BC.nms_image_class_via(mock_ops.nms_batched)
-        try:
-            yield
-        finally:
-            ops.ssd_decode_batched, ops.nms_image_class, ops.detection_pack = old
+    """the CPU stand-in of the library (tests/mock_ops.py), the batched tail included"""
+    return mock_ops.installed()
 
 
 def _canned_class(dets, native):
+    from odtk.heads import BatchedInference
     from odtk.voc_eval import EvaluateMixin
 
     class Canned(EvaluateMixin):
@@ -124,7 +93,7 @@ def _canned_class(dets, native):
         def __init__(self, config, data_provider):
             self.config, self.data_provider, self.mode = config, data_provider, config['mode']
             self.dev = torch.device('cpu')
-            self.batch_size = config['batch_size'] if self.mode == 'train' else self._test_batch_size(config)
+            self.batch_size = config['batch_size'] if self.mode == 'train' else BatchedInference._test_batch_size(config)
             self.calls, self.loaded = [], 0
             if self.mode == 'train':
                 self.val_generator, self.num_val = data_provider['val_generator'], data_provider['num_val']

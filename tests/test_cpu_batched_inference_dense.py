@@ -4,8 +4,7 @@
     csrc/detect_batched.hip), through the bodies of the GPU cases (tests/batched_dense_cases.py);
   * host logic over mocked launches: image slots by test_batch_size, its validation, staging errors, test_images against test_one_image of a model built
     without the key, the read-back layout of heads.CenterNetBatched.
-The mocks of the two batched decodes live here (per image, the single-image mocks of tests/mock_ops.py)."""
-import contextlib
+The mocks of the batched entry points are tests/mock_ops.py's (per image, its single-image stand-ins)."""
 import ctypes
 import os
 
@@ -59,33 +58,7 @@ def test_emulated_refinedet_decode_batched_and_tail():
 
 
 # ---------------------------------------------------------------- host logic over mocked launches
-def _centernet_decode_batched(keypoints, offset, size, stride, score_threshold, top_k, scores, bbox, class_id, counts, ws):
-    import mock_ops
-    for n in range(keypoints.shape[0]):
-        s, b, c = mock_ops.centernet_decode(keypoints[n], offset[n], size[n], stride, score_threshold, top_k, None)
-        k = len(s)
-        scores[n, :k] = s; bbox[n, :k] = b.reshape(-1, 4); class_id[n, :k] = c.to(torch.int32); counts[n] = k
-
-
-def _refinedet_decode_batched(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr, conf, boxes, keep, cand):
-    import mock_ops
-    for n in range(odm_conf.shape[0]):
-        for dst, src in zip((conf[n], boxes[n], keep[n], cand[n]), mock_ops.refinedet_decode(arm_loc[n], arm_conf[n], odm_loc[n], odm_conf[n], yx, hw, thr)):
-            dst.copy_(src)
-
-
-@contextlib.contextmanager
-def mocked():
-    from odtk import ops
-    with TB.mocked():
-        old = {k: getattr(ops, k) for k in ('centernet_decode_batched', 'refinedet_decode_batched', 'centernet_decode_workspace')}
-        ops.centernet_decode_batched, ops.refinedet_decode_batched = _centernet_decode_batched, _refinedet_decode_batched
-        ops.centernet_decode_workspace = lambda N, H, W, device: torch.zeros(4, dtype=torch.uint8)
-        try:
-            yield
-        finally:
-            for k, v in old.items():
-                setattr(ops, k, v)
+mocked = TB.mocked
 
 
 def _config(name, **kw):

@@ -1,5 +1,5 @@
-"""GPU: batched inference -- the tail of csrc/detect_batched.hip through the C-ABI, test_images() of the four native classes and of a fallback class,
-evaluate(batch_size=B).  The tail and compaction bodies are tests/batched_inference_cases.py (shared with the CPU tier, where the same kernels run from
+"""GPU: batched inference -- the tail of csrc/detect_batched.hip through the C-ABI, test_images() of the native classes and of a fallback class, a default
+model's test_one_image against the test-side single-image tail (tests/single_image_tail.py), evaluate(batch_size=B).  The tail and compaction bodies are tests/batched_inference_cases.py (shared with the CPU tier, where the same kernels run from
 source under the emulation)."""
 import os
 import sys
@@ -223,32 +223,59 @@ def test_retinanet_test_images_vs_oracle(retinanet_case, dev):
     assert total > 0
 
 
-def test_retinanet_test_images_above_the_nms_capacity(retinanet_case, dev):
-    """RetinaNet at 448 x 448 has 37 629 anchors, more than the NMS takes per problem: test_images goes through odtk_compact_rows / odtk_gather_rows.  On the
-    model's own head outputs the single-image tail (heads.retina_detect: torch.nonzero + gathers) must give the same arrays, ==, for every image."""
-    from odtk import heads
-    TR, p, _, _ = retinanet_case
+def _above_the_nms_capacity(TR, p, B):
+    """RetinaNet at 448 x 448 has 37 629 anchors, more than the NMS takes per problem: the tail goes through odtk_compact_rows / odtk_gather_rows.  On the
+    model's own head outputs the single-image tail (single_image_tail.retina_detect: torch.nonzero + gathers) must give the same arrays, ==, for every
+    image.  B = None: a model built WITHOUT test_batch_size, fed one image at a time through test_one_image."""
+    from single_image_tail import retina_detect
     imgs, _ = TR._batch(2, 448, 96)
-    m = TR._model('test', 'f32', 1, 448, nms_score_threshold=0.999, test_batch_size=2)
+    m = TR._model('test', 'f32', 1, 448, nms_score_threshold=0.999, **({} if B is None else {'test_batch_size': B}))
     m.load_oracle_params(p)
-    m.test_images(imgs.numpy())
+    x = imgs.numpy()
+    run = m.test_images if B else (lambda xs: [m.test_one_image(xs[n: n + 1]) for n in range(xs.shape[0])])
+    run(x[:B or 1])
     t = m._tail_batched
-    assert m.pconf.shape[1] == 37629 and t.compact
+    assert m.batch_size == (B or 1) and m.pconf.shape[1] == 37629 and t.compact
     # a threshold that leaves ~3 000 candidate rows per image (random weights: at the parity test's 0.15 nearly every anchor is one): from the decoded scores
     best = t.conf.max(dim=2).values * t.keep
-    thr = float(torch.topk(best.flatten(), 6000).values[-1])
+    thr = float(torch.topk(best.flatten(), 3000 * (B or 1)).values[-1])
     assert 0.0 < thr < 0.999
     m.nms_score_threshold = thr
-    got = m.test_images(imgs.numpy())
-    assert 0 < int(t.row_cnt.max()) <= 32768 and int(t.row_cnt.sum()) >= 6000
     total = 0
-    for n in range(2):
-        s, b, c = heads.retina_detect(m.pconf[n], m.pbox[n], m.anc[2], m.anc[3], thr, m.nms_max_boxes, m.nms_iou_threshold)
-        assert _same(got[n], [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()]), n
-        total += len(got[n][0])
+    if B:
+        got = run(x)
+        assert 0 < int(t.row_cnt.max()) <= 32768 and int(t.row_cnt.sum()) >= 6000
+        for n in range(2):
+            s, b, c = retina_detect(m.pconf[n], m.pbox[n], m.anc[2], m.anc[3], thr, m.nms_max_boxes, m.nms_iou_threshold)
+            assert _same(got[n], [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()]), n
+            total += len(got[n][0])
+        rev = run(x[::-1].copy())
+        assert _same(rev[0], got[1]) and _same(rev[1], got[0])
+    else:
+        for n in range(2):
+            got = m.test_one_image(x[n: n + 1])
+            assert 0 < int(t.row_cnt[0]) <= 32768 and (n == 1 or int(t.row_cnt[0]) >= 3000)
+            s, b, c = retina_detect(m.pconf[0], m.pbox[0], m.anc[2], m.anc[3], thr, m.nms_max_boxes, m.nms_iou_threshold)
+            assert _same(got, [s.cpu().numpy(), b.cpu().numpy().reshape(-1, 4), c.cpu().numpy()]), n
+            total += len(got[0])
     assert total > 0
-    rev = m.test_images(imgs.numpy()[::-1].copy())
-    assert _same(rev[0], got[1]) and _same(rev[1], got[0])
+    return m, x
+
+
+def test_retinanet_test_images_above_the_nms_capacity(retinanet_case, dev):
+    TR, p, _, _ = retinanet_case
+    _above_the_nms_capacity(TR, p, 2)
+
+
+def test_retinanet_default_model_above_the_nms_capacity_and_overflow(retinanet_case, dev):
+    """the same comparison for a model built without test_batch_size: test_one_image takes odtk_compact_rows / odtk_gather_rows where the single-image tail
+    takes torch.nonzero.  Then more candidate rows than the NMS takes per problem: the ValueError of the batched tail, naming image 0"""
+    TR, p, _, _ = retinanet_case
+    m, x = _above_the_nms_capacity(TR, p, None)
+    best = m._tail_batched.conf.max(dim=2).values * m._tail_batched.keep
+    m.nms_score_threshold = float(torch.topk(best.flatten(), 33000).values[-1])          # at least 33 000 of the 37 629 rows are candidates
+    with pytest.raises(ValueError, match=r'image 0: \d+ candidate boxes exceed the NMS capacity of 32768'):
+        m.test_one_image(x[1:2])
 
 
 # ---------------------------------------------------------------- 4: independence of the images
@@ -286,23 +313,59 @@ def test_retinanet_images_are_independent(retinanet_case, dev):
     _independence(retinanet_case[3], retinanet_case[2])
 
 
-# ---------------------------------------------------------------- 5: the default is unchanged
-def test_default_model_test_one_image_equals_test_images_of_one(ssd300_case, dev):
-    _, imgs, _, m, one = ssd300_case
-    assert one.batch_size == 1 and tuple(one.images.shape) == (1, 300, 300, 3) and tuple(one.d_conf.shape) == (8828, 20)
-    for thr in (0.5, 0.2):
-        one.nms_score_threshold = m.nms_score_threshold = thr
-        for n in range(2):
-            a = one.test_one_image(imgs[n: n + 1].numpy())
-            b = one.test_images(imgs[n: n + 1].numpy())
-            assert len(b) == 1 and _same(a, b[0]), (thr, n)
-        assert sum(len(one.test_one_image(imgs[n: n + 1].numpy())[0]) for n in range(2)) > 0
-    one.nms_score_threshold = m.nms_score_threshold = 0.5
-    with pytest.raises(ValueError, match='test_images'):
-        one.test_images(imgs[:2].numpy())
-    with pytest.raises(ValueError, match='test_batch_size'):
-        import odtk
-        odtk.SSD300(dict(SSD_CONFIG, test_batch_size=0), None)
+# ---------------------------------------------------------------- 5: the default model (no test_batch_size): test_one_image is the batched path with one image
+def _default_model(name, ssd300_case, yolov3_case, retinanet_case):
+    """-> (model built WITHOUT test_batch_size at the smallest input its tests build it at, on calibrated oracle weights; two pictures; two thresholds)"""
+    import odtk
+    import test_gpu_batched_inference_dense as TD
+    if name == 'SSD300':
+        return ssd300_case[4], ssd300_case[1][:2].numpy(), (0.5, 0.2)
+    if name == 'SSD512':
+        from oracle import ssd512_ref as R5
+        imgs, _ = R5.synthetic_batch(2, 45)
+        p = R5.init_params(3)
+        R5.calibrate_bn(p, imgs, subtract_mean=False)
+        m = odtk.SSD512(dict(SSD_CONFIG), None)
+        m.load_oracle_params(p)
+        return m, imgs.numpy(), (0.5, 0.2)
+    if name == 'YOLOv3':
+        import test_gpu_yolov3 as TY
+        m = TY._model('test', 'f32', 1, 64, nms_score_threshold=0.5)
+        m.load_oracle_params(yolov3_case[1])
+        return m, TY._batch(2, 64, 60)[0].numpy(), (0.5, 0.3)
+    if name == 'RetinaNet':
+        TR = retinanet_case[0]
+        m = TR._model('test', 'f32', 1, 128, nms_score_threshold=0.15)
+        m.load_oracle_params(retinanet_case[1])
+        return m, TR._batch(2, 128, 95)[0].numpy(), (0.15, 0.05)
+    T = __import__({'CenterNet': 'test_gpu_centernet_model', 'RefineDet320': 'test_gpu_refinedet_model', 'PFPNetR': 'test_gpu_pfpnet_model'}[name])
+    p = T.NR.init_params({'CenterNet': 19, 'RefineDet320': 29, 'PFPNetR': 39}[name])
+    imgs, _ = T._batch(3, 150 if name == 'CenterNet' else 220)
+    if name == 'CenterNet':
+        p['c63.beta'] = p['c63.beta'] + 1.0
+        TD._calibrated(T.NR, p, imgs, normalize=False)
+        m = T._model('test', 1, top_k_results_output=10)
+    else:
+        TD._calibrated(T.NR, p, imgs, subtract_mean=False)
+        m = T._model('test', 1)
+    m.load_oracle_params(p)
+    return m, imgs[:2].numpy(), DEFAULT_THRESHOLDS[name]
+
+
+DEFAULT_THRESHOLDS = {'CenterNet': (0.3, 0.1), 'RefineDet320': (0.3, 0.1), 'PFPNetR': (0.3, 0.1)}
+
+
+@pytest.mark.parametrize('name', ['SSD300', 'SSD512', 'YOLOv3', 'RetinaNet', 'CenterNet', 'RefineDet320', 'PFPNetR'])
+def test_default_model_test_one_image_equals_test_images_of_one(name, ssd300_case, yolov3_case, retinanet_case, dev):
+    """BC.check_default_model: test_one_image of a default model == the test-side single-image tail on the model's own head tensors == test_images(...)[0]"""
+    m, imgs, thresholds = _default_model(name, ssd300_case, yolov3_case, retinanet_case)
+    assert type(m).__name__ == name
+    BC.check_default_model(m, imgs, thresholds, m.top_k_results_output if name == 'CenterNet' else m.nms_max_boxes)
+    if name == 'SSD300':
+        assert tuple(m.images.shape) == (1, 300, 300, 3) and tuple(m._tail_batched.conf.shape) == (1, 8828, 20)
+        with pytest.raises(ValueError, match='test_batch_size'):
+            import odtk
+            odtk.SSD300(dict(SSD_CONFIG, test_batch_size=0), None)
 
 
 # ---------------------------------------------------------------- 6: evaluate

@@ -78,8 +78,9 @@ def test_inference_tail_matches_reference_detections(dev):
     heads = _heads()
     g, arm_loc, arm_conf, odm_loc, odm_conf, _ = _inputs(dev)
     anc_d = heads.refinedet_anchors(320, dev)
-    s, b, c = heads.refinedet_detect(arm_loc[0].to(dev).contiguous(), arm_conf[0].to(dev).contiguous(), odm_loc[0].to(dev).contiguous(),
-                                     odm_conf[0].to(dev).contiguous(), anc_d[2], anc_d[3], 0.12, 10, 0.45)
+    from single_image_tail import refinedet_detect
+    s, b, c = refinedet_detect(arm_loc[0].to(dev).contiguous(), arm_conf[0].to(dev).contiguous(), odm_loc[0].to(dev).contiguous(),
+                               odm_conf[0].to(dev).contiguous(), anc_d[2], anc_d[3], 0.12, 10, 0.45)
     torch.cuda.synchronize()
     assert c.cpu().tolist() == g['det_class'].tolist() and len(s) == 200
     assert np.allclose(s.cpu().numpy(), g['det_scores'], atol=1e-6)

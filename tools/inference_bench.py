@@ -1,7 +1,8 @@
 """Inference and evaluation rates, per-image path against batched path, in ONE process on ONE set of weights; prints one JSON line.
 
 Per class and engine (--classes ssd300,ssd512,yolov3,retinanet,centernet,refinedet,pfpnet; engines of the class or --engines):
-  * the loop of test_one_image (the per-image path: a model built without test_batch_size);
+  * the loop of test_one_image on a model built without test_batch_size.  Since the seven classes share one inference path (heads.BatchedInference) this row
+    and the B = 1 row below time the SAME code; the row stays so that runs of this tool on older commits, where it was the separate per-image tail, compare;
   * test_images at B = 1, 8, 32 (16 for RetinaNet 800 x 800) on models built with test_batch_size = B from the same weights;
   * evaluate() at batch_size 1 and at the largest B over the same validation generator, with the share of the wall time spent in Python staging
     (VOCEvaluator.add) and in result();
