@@ -1,18 +1,24 @@
-"""The host plumbing every detector class shares: the flat parameter store, the constructor prologue, batch staging, the epoch loop, torch
-checkpoints and the data-parallel hook.  No kernel launch order lives here: a class still owns its layer list, `_build`, `_forward`, `_loss`,
-`_backward_iter` and `_train_step_engine`.
+"""The host plumbing every detector class shares: the flat parameter store, the constructor prologue, batch staging, the step skeleton, the epoch
+loop, torch and tf.train.Saver checkpoints and the data-parallel hook.  No kernel launch order lives here: a class still owns its layer list, `_build`,
+`_forward`, `_loss` and `_backward_iter`.  (ssd300.SSD300 keeps a step of its own: three streams, recorded lists, split graphs.)
 
 What a class provides:
   * `specs` and the layout: `pinfo` (and `sinfo` if it has moving statistics) name -> (offset, shape) into the flat buffers, then `_alloc_flat`;
   * `_logical_cin(layer)`: the un-padded input-channel count of a layer's filter (`get_param` cuts the pad channels off with it);
-  * optional hooks: `_check_oracle_param(name, value)` (load_oracle_params), PROGRESS_FROM, OPT_BUFFERS / OPT_BLOB_KEYS;
-  * `_prologue(...)` at the top of its constructor, then `_set_engine(...)` with its own engine default.
+  * `_prologue(...)` at the top of its constructor, then `_set_engine(...)` with its own engine default;
+  * the step: `_forward(training)`, `_loss(grad_scale)`, `_backward_iter()` and `_step_loss()`, the value train_step returns.  Where it differs from the
+    default: `_loss_scale()`, `_layer_ready(name)`, `_optimizer_step(lr)`; `use_graph` = True replays forward + loss + backward from one HIP graph;
+  * the Saver files: `tf_variable_map()` (our name -> the reference graph's variable name) and OPT_SLOT_SCOPE.  Where it differs: OPT_SLOTS,
+    `_to_tf` / `_from_tf` (kernel layouts), `_tf_extra_variables()`, `_tf_is_backbone(ours, tfname)`, TF_STATS_OPTIONAL, OPT_SLOTS_STRICT;
+  * optional: `_check_oracle_param(name, value)` (load_oracle_params), PROGRESS_FROM, OPT_BUFFERS / OPT_BLOB_KEYS / OPT_NOT_RESTORED.
 A class on the f32 warm-up lists warmup.F32Warmup in front of this one (its `set_batch` / `train_step` / `save_weight` wrap the `_engine` methods here).
 """
 from __future__ import annotations
 
 import os
 import sys
+import warnings
+import zipfile
 from collections import OrderedDict
 
 import numpy as np
@@ -23,13 +29,16 @@ from ._lib import BF16, F32, F32X3
 
 
 class _Act:
-    """rows x pitch activation; `gid` names the gradient buffer it shares with its residual partners"""
+    """rows x pitch activation.  Its gradient: `gid` names the buffer it shares with its residual partners (YOLOv3, RetinaNet, FCOS), or `g` is the
+    buffer itself, allocated by the class's _build_backward (CenterNet, RefineDet320).  `vgg`: a bias + ReLU layer's output (its ReLU mask is the
+    activation); alloc=False: a prediction layer whose rows live in the class's prediction tensor"""
 
-    def __init__(self, name, N, H, W, C, ld, dtype, dev):
-        self.name, self.N, self.H, self.W, self.C, self.ld = name, N, H, W, C, ld
+    def __init__(self, name, N, H, W, C, ld, dtype, dev, vgg=False, alloc=True):
+        self.name, self.N, self.H, self.W, self.C, self.ld, self.vgg = name, N, H, W, C, ld, vgg
         self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev)
+        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev) if alloc else None
         self.gid = name
+        self.g = None
 
 
 def store_padded(name, dst, value):
@@ -46,8 +55,17 @@ def store_padded(name, dst, value):
 class DetectorBase:
     OPT_BUFFERS = ('Mom',)            # flat optimizer-state buffers laid out like P (CenterNet: ('M1', 'M2')) ...
     OPT_BLOB_KEYS = ('momentum',)     # ... and the keys they have in a torch checkpoint (part of the file format)
+    OPT_NOT_RESTORED = ('the parameter layout of the checkpoint differs from this model ({} vs {} entries): '
+                        'momentum NOT restored (it stays as it is) although global_step is')
+    OPT_SLOTS = ('Momentum',)         # ... and the slot variables `<scope><variable>/<slot>` they are in a tf.train.Saver file (CenterNet: ('Adam', 'Adam_1'))
+    OPT_SLOT_SCOPE = ''               # the variable scope that is open where the reference creates its optimizer, with its '/'
+    OPT_SLOTS_STRICT = False          # restore: a slot is found by suffix under ANY scope and a missing one is passed over in silence; True (CenterNet):
+                                      # only under '' or OPT_SLOT_SCOPE, and missing ones are warned about (global_step drives Adam's bias correction)
+    TF_STATS_OPTIONAL = False         # restore: a moving statistic absent from the file is skipped (RetinaNet: a pre-training file holds none)
     PROGRESS_FROM = 0                 # train_one_epoch prints the iteration counted from here: each reference file's own print
     sinfo = {}                        # a class without moving statistics (FCOS) leaves it empty and has no S
+    use_graph = False                 # the step's forward + loss + backward replay from one HIP graph (a class reads it from its config)
+    _graph, _graph_gt, _eager_steps = None, None, 0
 
     # ------------------------------------------------------------------ constructor prologue
     def _prologue(self, config, data_provider, native_test_batch=False, nms=True, num_val_optional=False):
@@ -136,10 +154,15 @@ class DetectorBase:
             v = v[..., : self._logical_cin(name[:-2])].contiguous()
         return v
 
-    def _logical(self, name, buf):
+    def _to_tf(self, name, buf):
         """parameter `name` out of a flat buffer (P or an optimizer buffer) in TensorFlow's layout: kernels HWIO (transposed convs [h, w, out, in]), un-padded"""
         v = self.get_param(name, buf)
         return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
+
+    def _from_tf(self, name, array):
+        """the inverse: a variable of a tf.train.Saver file in the layout set_param takes"""
+        v = torch.from_numpy(np.asarray(array))
+        return v.permute(3, 0, 1, 2).contiguous() if name.endswith('.w') else v
 
     def _check_oracle_param(self, name, value):
         """hook of load_oracle_params: raise for a value this class cannot hold"""
@@ -187,6 +210,61 @@ class DetectorBase:
 
     def _gt_reshaped(self, shape):
         """hook of _set_batch_engine: the ground-truth buffer was (re)allocated with this shape"""
+
+    def _stage_test_image(self, images):
+        """the one image of a batch-1 test-mode model into self.images (the classes without a batched test_images)"""
+        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
+        if self.data_format == 'channels_first' and images.shape[1] == 3:
+            images = images.permute(0, 2, 3, 1)
+        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
+        self.images.copy_(images)
+
+    # ------------------------------------------------------------------ the optimizer step
+    def _loss_scale(self):
+        """what the loss kernels scale their gradients with: d(mean over the images of the GLOBAL batch)"""
+        return 1.0 / self.loss_divisor_batch
+
+    def _layer_ready(self, name):
+        """data parallel: `_backward_iter` yielded `name`, every gradient of that layer and of all later layers has been launched"""
+        self.dist.layer_ready(name)
+
+    def _step_body(self):
+        self.G.zero_()
+        self._forward(True)
+        self._loss(self._loss_scale())
+        for name in self._backward_iter():
+            if self.dist is not None:
+                self._layer_ready(name)
+
+    def _optimizer_step(self, lr):
+        """MomentumOptimizer(0.9) over the whole flat buffer, the sum of squares of the PRE-update weights into l2_sum, then the step counter"""
+        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
+        ops.sum_f32(self.l2_partial, self.l2_sum)
+        self.global_step += 1
+
+    def _train_step_engine(self, lr):
+        """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor.
+        use_graph, single device: after two eager steps (the library's lazily grown scratch buffers exist by then) forward + loss + backward replay from
+        ONE HIP graph -- the dependent launches leave the queue without host round trips; the optimizer launches stay outside (lr is a launch
+        argument).  Which classes gain from it is measured, and written where the class reads 'use_graph'.  Data parallel / sync-BN: eager (collectives
+        inside the step)."""
+        if self.dist is not None:
+            self.dist.begin_step()
+        if self.use_graph and self.dist is None and self.dev.type == 'cuda' and self._eager_steps >= 2:
+            if self._graph is None or self._graph_gt is not self.gt:
+                self._graph = torch.cuda.CUDAGraph()
+                self._graph_gt = self.gt                       # the captured launches hold this buffer's pointer and pad length
+                with torch.cuda.graph(self._graph):
+                    self._step_body()
+            self._graph.replay()
+        else:
+            self._step_body()
+            self._eager_steps += 1
+        if self.dist is not None:
+            self.dist.finish_step()
+        self._optimizer_step(lr)
+        self._fp_batch.run()
+        return self._step_loss()
 
     def train_one_epoch(self, lr):
         if callable(self.train_initializer):
@@ -244,14 +322,85 @@ class DetectorBase:
             raise ValueError(f'{path}: {len(unknown)} parameters of the checkpoint are not part of this model (e.g. {unknown[:3]}): '
                              'it was written by a different layer layout')
         self.load_oracle_params(blob['params'])
-        if tuple(blob['momentum'].shape) == tuple(self.Mom.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.Mom.copy_(blob['momentum'].to(self.dev))
+        state = [(blob[key], getattr(self, name)) for key, name in zip(self.OPT_BLOB_KEYS, self.OPT_BUFFERS)]
+        if all(tuple(saved.shape) == tuple(buf.shape) for saved, buf in state) and dict(blob['layout']) == dict(self.pinfo):
+            for saved, buf in state:
+                buf.copy_(saved.to(self.dev))
         else:
-            import warnings
-            warnings.warn(f'{path}: the parameter layout of the checkpoint differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): '
-                          'momentum NOT restored (it stays as it is) although global_step is', RuntimeWarning)
+            warnings.warn(f'{path}: ' + self.OPT_NOT_RESTORED.format(len(blob['layout']), len(self.pinfo)), RuntimeWarning)
         self.global_step = int(blob.get('global_step', 0))
         print('load weight', path, 'successfully')
+
+    # ------------------------------------------------------------------ tf.train.Saver checkpoints (tf_checkpoint.py)
+    def tf_variable_map(self):
+        """OrderedDict our parameter / statistic name -> the variable's name in the reference's graph, in the order the class exports them"""
+        raise NotImplementedError
+
+    def _tf_extra_variables(self):
+        """what the reference's Saver writes besides weights, statistics, slots and global_step (CenterNet: Adam's beta powers)"""
+        return {}
+
+    def _tf_is_backbone(self, ours, tfname):
+        """is this one of the variables the reference's pre-training Saver restores: the trainables under 'backone' (sic), in most of its files"""
+        return tfname.startswith('backone') and ours in self.pinfo
+
+    def export_tf_variables(self):
+        """what the reference's `tf.train.Saver()` writes: every variable of its graph under its name (tf_variable_map) -- weights and moving
+        statistics --, the optimizer's slots `<OPT_SLOT_SCOPE><variable>/<slot>` and global_step"""
+        self._sync_from_twin()
+        out = OrderedDict()
+        for ours, tfname in self.tf_variable_map().items():
+            if ours in self.pinfo:
+                out[tfname] = self._to_tf(ours, self.P)
+                for slot, buf in zip(self.OPT_SLOTS, self.OPT_BUFFERS):
+                    out[f'{self.OPT_SLOT_SCOPE}{tfname}/{slot}'] = self._to_tf(ours, getattr(self, buf))
+            else:
+                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
+        out.update(self._tf_extra_variables())
+        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
+        return out
+
+    def load_tf_checkpoint(self, path, backbone_only=False):
+        """`saver.restore(sess, path)` from tf.train.Saver files (ours or the reference's): weights, moving statistics, optimizer slots, global_step;
+        backbone_only: what the reference's pre-training Saver restores (`_tf_is_backbone`), nothing else"""
+        from .tf_checkpoint import NewCheckpointReader
+        if getattr(self, 'f32_warmup_steps', 0):
+            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
+        reader = NewCheckpointReader(str(path))
+        names = list(reader.get_variable_to_shape_map())
+        missing = []
+        for ours, tfname in self.tf_variable_map().items():
+            if backbone_only and not self._tf_is_backbone(ours, tfname):
+                continue
+            if ours in self.sinfo:
+                if reader.has_tensor(tfname) or not self.TF_STATS_OPTIONAL:
+                    self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
+                continue
+            self.set_param(ours, self._from_tf(ours, reader.get_tensor(tfname)))          # KeyError = Saver's NotFoundError
+            for slot, buf in () if backbone_only else zip(self.OPT_SLOTS, self.OPT_BUFFERS):
+                # the slot's scope prefix is whatever scope the optimizer was created in: match by suffix
+                slot = f'{tfname}/{slot}'
+                found = [n for n in names if n.endswith(slot) and (not self.OPT_SLOTS_STRICT or n[: len(n) - len(slot)] in ('', self.OPT_SLOT_SCOPE))]
+                if found:
+                    self.set_param(ours, self._from_tf(ours, reader.get_tensor(found[0])), getattr(self, buf))
+                else:
+                    missing.append(slot)
+        if not backbone_only and reader.has_tensor('global_step'):
+            self.global_step = int(reader.get_tensor('global_step'))
+        if missing and self.OPT_SLOTS_STRICT:
+            warnings.warn(f'{path}: {len(missing)} {self.OPT_SLOTS[0]} slot variables not in the checkpoint (e.g. {missing[0]}): their moments stay as they are, '
+                          f'while global_step = {self.global_step} drives the bias correction', RuntimeWarning)
+        self._refresh_operand_copies()
+
+    def _load_backbone_weight(self, path, message):
+        """the backbone's variables (`_tf_is_backbone`) from a tf.train.Saver checkpoint or from a torch file (a zip archive) of save_weight"""
+        if os.path.exists(str(path) + '.index') or not zipfile.is_zipfile(str(path)):
+            self.load_tf_checkpoint(path, backbone_only=True)
+        else:
+            names = self.tf_variable_map()
+            blob = torch.load(path, map_location='cpu', weights_only=True)['params']
+            self.load_oracle_params({k: v for k, v in blob.items() if k in names and self._tf_is_backbone(k, names[k])})
+        print(message, path, 'successfully')
 
     def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
         from .dist import GradAllReducer

@@ -22,7 +22,6 @@ residuals cover one sum per activation only).
 from __future__ import annotations
 
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -30,14 +29,13 @@ import torch
 
 from . import heads, ops
 from ._lib import BF16
-from .base import DetectorBase
+from .base import DetectorBase, _Act
 from .warmup import F32Warmup
 
 MEAN = (0.485, 0.456, 0.406)                                  # CenterNet.py:52-53
 STD = (0.229, 0.224, 0.225)
 STRIDE = 4.0                                                   # :126
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8                  # tf.train.AdamOptimizer defaults (:154)
-ADAM_SLOT_SCOPE = 'center_detector/'                            # optimizer.minimize is called inside this variable scope (CenterNet.py:131-156)
 
 
 def layer_specs(num_classes):
@@ -75,17 +73,15 @@ def layer_specs(num_classes):
     return specs
 
 
-class _Act:
-    def __init__(self, name, N, H, W, C, ld, dtype, dev):
-        self.name, self.N, self.H, self.W, self.C, self.ld = name, N, H, W, C, ld
-        self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev)
-        self.g = None                                          # gradient buffer (train mode, allocated by _build_backward)
-
-
 class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
     OPT_BUFFERS = ('M1', 'M2')                                 # Adam's m and v
     OPT_BLOB_KEYS = ('adam_m', 'adam_v')
+    OPT_NOT_RESTORED = 'parameter layout differs from this model ({} vs {} entries): Adam moments NOT restored'
+    OPT_SLOTS = ('Adam', 'Adam_1')
+    # `optimizer.minimize` runs INSIDE `with tf.variable_scope('center_detector')` (CenterNet.py:131-156), and both the slot creator
+    # (`variable_scope(None, primary.op.name + '/Adam')`) and the non-slot accumulators take the enclosing scope as a prefix
+    OPT_SLOT_SCOPE = 'center_detector/'
+    OPT_SLOTS_STRICT = True
     PROGRESS_FROM = 1                                          # CenterNet.py's epoch loop prints i + 1
 
     def __init__(self, config, data_provider):
@@ -374,25 +370,16 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
                 self._fold(x, acc)
 
     # ------------------------------------------------------------------ public: training
-    def _train_step_engine(self, lr):
-        """one AdamOptimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
-        if self.dist is not None:
-            self.dist.begin_step()
-        self.G.zero_()
-        self._forward(True)
-        self._loss(1.0 / self.loss_divisor_batch)
-        for name in self._backward_iter():
-            if self.dist is not None:
-                self.dist.layer_ready(name)
-        if self.dist is not None:
-            self.dist.finish_step()
+    def _optimizer_step(self, lr):
+        """AdamOptimizer: the step counter first, its bias correction needs t"""
         self.global_step += 1
         t = self.global_step
         lr_t = lr * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
         ops.adam(self.P, self.M1, self.M2, self.G, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, self.weight_decay, 1.0, self.l2_partial,
                  self.Pc if self.DT == BF16 else None)
         ops.sum_f32(self.l2_partial, self.l2_sum)
-        self._fp_batch.run()
+
+    def _step_loss(self):
         return self.loss_parts[:, 3].mean() + self.weight_decay * self.l2_sum          # CenterNet.py:152-153 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
@@ -408,84 +395,18 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
         t.launch(self.keypoints, self.offset, self.size, self.score_threshold, STRIDE)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def export_tf_variables(self):
-        """what the reference's `tf.train.Saver()` (CenterNet.py:296-301) would write: weights, moving statistics, global_step and AdamOptimizer's state --
-        slots `center_detector/<variable>/Adam` (m), `…/Adam_1` (v) and the accumulators `center_detector/beta1_power` / `beta2_power`
-        (= beta^(t + 1) after t steps): `optimizer.minimize` runs INSIDE `with tf.variable_scope('center_detector')` (:131-156), and both the slot
-        creator (`variable_scope(None, primary.op.name + '/Adam')`) and the non-slot accumulators take the enclosing scope as a prefix"""
-        self._sync_from_twin()
-        out = OrderedDict()
-        for tfname, ours in reference_variable_map(self.num_classes).items():
-            if ours in self.pinfo:
-                out[tfname] = self._logical(ours, self.P)
-                out[ADAM_SLOT_SCOPE + tfname + '/Adam'] = self._logical(ours, self.M1)
-                out[ADAM_SLOT_SCOPE + tfname + '/Adam_1'] = self._logical(ours, self.M2)
-            else:
-                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
-        out[ADAM_SLOT_SCOPE + 'beta1_power'] = np.asarray(ADAM_B1 ** (self.global_step + 1), dtype=np.float32)
-        out[ADAM_SLOT_SCOPE + 'beta2_power'] = np.asarray(ADAM_B2 ** (self.global_step + 1), dtype=np.float32)
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
+    def tf_variable_map(self):
+        """the variables of the reference's `tf.train.Saver()` (CenterNet.py:296-301)"""
+        return OrderedDict((ours, tfname) for tfname, ours in reference_variable_map(self.num_classes).items())
 
-    def load_tf_checkpoint(self, path, backbone_only=False):
-        """`saver.restore` (CenterNet.py:321-327) from tf.train.Saver files; backbone_only = the `pretrained_saver` over the trainables of 'backone'"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = list(reader.get_variable_to_shape_map())
-        missing_slots = []
-        for tfname, ours in reference_variable_map(self.num_classes).items():
-            if backbone_only and not (tfname.startswith('backone/') and ours in self.pinfo):
-                continue
-            v = torch.from_numpy(reader.get_tensor(tfname))                     # KeyError = Saver's NotFoundError
-            if ours in self.pinfo:
-                self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-                for slot, buf in (('/Adam', self.M1), ('/Adam_1', self.M2)):
-                    if backbone_only:
-                        continue
-                    # the slot's scope prefix is whatever scope the optimizer was created in ('center_detector/' in the reference): match by suffix
-                    found = [n for n in names if n.endswith(tfname + slot) and n[: len(n) - len(tfname + slot)] in ('', ADAM_SLOT_SCOPE)]
-                    if not found:
-                        missing_slots.append(tfname + slot)
-                    else:
-                        mv = torch.from_numpy(reader.get_tensor(found[0]))
-                        self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, buf)
-            else:
-                self.stat(ours).copy_(v.to(self.dev))
-        if not backbone_only and reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        if missing_slots:
-            import warnings
-            warnings.warn(f'{path}: {len(missing_slots)} Adam slot variables not in the checkpoint (e.g. {missing_slots[0]}): their moments stay as they are, '
-                          f'while global_step = {self.global_step} drives the bias correction', RuntimeWarning)
-        self._refresh_operand_copies()
-
-    def load_weight(self, path):
-        if os.path.exists(str(path) + '.index'):                 # a tf.train.Saver checkpoint prefix
-            self.load_tf_checkpoint(path)
-            print('load weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)
-        self.load_oracle_params(blob['params'])
-        if tuple(blob['adam_m'].shape) == tuple(self.M1.shape) and dict(blob['layout']) == dict(self.pinfo):
-            self.M1.copy_(blob['adam_m'].to(self.dev)); self.M2.copy_(blob['adam_v'].to(self.dev))
-        else:
-            import warnings
-            warnings.warn(f'{path}: parameter layout differs from this model ({len(blob["layout"])} vs {len(self.pinfo)} entries): Adam moments NOT restored',
-                          RuntimeWarning)
-        self.global_step = int(blob.get('global_step', 0))
-        print('load weight', path, 'successfully')
+    def _tf_extra_variables(self):
+        """AdamOptimizer's accumulators `center_detector/beta1_power` / `beta2_power` (= beta^(t + 1) after t steps)"""
+        return {self.OPT_SLOT_SCOPE + 'beta1_power': np.asarray(ADAM_B1 ** (self.global_step + 1), dtype=np.float32),
+                self.OPT_SLOT_SCOPE + 'beta2_power': np.asarray(ADAM_B2 ** (self.global_step + 1), dtype=np.float32)}
 
     def load_pretrained_weight(self, path):
         """CenterNet.py:321-323: `pretrained_saver` restores the trainable variables under 'backone' (c0 .. c49)"""
-        if os.path.exists(str(path) + '.index'):
-            self.load_tf_checkpoint(path, backbone_only=True)
-            print('load pretrained weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)['params']
-        self.load_oracle_params({k: v for k, v in blob.items() if k in self.pinfo and int(k[1:].split('.')[0]) < 50})
-        print('load pretrained weight', path, 'successfully')
+        self._load_backbone_weight(path, 'load pretrained weight')
 
 
 def reference_variable_map(num_classes=20):

@@ -18,14 +18,12 @@ Group norm has no batch statistics: nothing like moving averages exists, and dat
 from __future__ import annotations
 
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16
 from .base import DetectorBase, _Act
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
@@ -273,7 +271,7 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
         pname = pname or name
         ops.gn_fwd(x.t, x.ld, y.t, y.ld, x.N, x.H * x.W, x.C, GROUPS, self.param(pname + '.gamma'), self.param(pname + '.beta'), 1, self.gnsave[name])
 
-    def _forward(self, subtract_mean=True):
+    def _forward(self, training=True, subtract_mean=True):          # (group norm: nothing depends on `training`)
         ops.preprocess(self.images, MEAN_RGB if subtract_mean else (0., 0., 0.), self.input.ld, self.DT, self.input.t)
         for op in self.plan:
             kind = op[0]
@@ -341,77 +339,27 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
                 yield name
 
     # ------------------------------------------------------------------ public: training
-    def _train_step_engine(self, lr):
-        """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
-        if self.dist is not None:
-            self.dist.begin_step()
-        self.G.zero_()
-        self._forward()
-        self._loss(1.0 / self.loss_divisor_batch)
-        for name in self._backward_iter():
-            if self.dist is not None:
-                self.dist.layer_ready(name)
-        if self.dist is not None:
-            self.dist.finish_step()
-        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
-        ops.sum_f32(self.l2_partial, self.l2_sum)
-        self._fp_batch.run()
-        self.global_step += 1
+    def _step_loss(self):
         return self.loss_img.mean() + self.weight_decay * self.l2_sum                              # FCOS.py:186-187
 
     # ------------------------------------------------------------------ public: inference
     def test_one_image(self, images):
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
-        self._forward(subtract_mean=bool(self.config.get('test_subtract_mean', False)))
+        self._stage_test_image(images)
+        self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
         scores, bbox, cid = heads.fcos_detect([t[0] for t in self.conf], [t[0] for t in self.reg], [t[0] for t in self.center],
                                               self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold)
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def export_tf_variables(self):
-        """what the reference's `tf.train.Saver()` (FCOS.py:390-394) writes: every variable under its name (reference_variable_map),
-        global_step, and the momentum slots `<variable>/Momentum` created under the 'head' scope of the graph (:111, :188)"""
-        self._sync_from_twin()
-        out = OrderedDict()
-        for tfname, ours in reference_variable_map().items():
-            out[tfname] = self._logical(ours, self.P)
-            out[f'head/{tfname}/Momentum'] = self._logical(ours, self.Mom)
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
+    OPT_SLOT_SCOPE = 'head/'                # the momentum slots are created under the 'head' scope of the graph (FCOS.py:111, :188)
 
-    def load_tf_checkpoint(self, path, backbone_only=False):
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        for tfname, ours in reference_variable_map().items():
-            if backbone_only and not tfname.startswith('backone'):
-                continue
-            v = torch.from_numpy(reader.get_tensor(tfname))
-            self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-            slot = [k for k in names if k.endswith(tfname + '/Momentum')]
-            if slot and not backbone_only:
-                mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
-        if not backbone_only and reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+    def tf_variable_map(self):
+        """the variables of the reference's `tf.train.Saver()` (FCOS.py:390-394)"""
+        return OrderedDict((ours, tfname) for tfname, ours in reference_variable_map().items())
 
     def load_pretrained_weight(self, path):
         """FCOS.py:434-436 restores the 'backone' variables: here the stem + unit layers of a saved file"""
-        if os.path.exists(str(path) + '.index'):
-            self.load_tf_checkpoint(path, backbone_only=True)
-            print('load pretrained weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)['params']
-        nb = 1 + 4 * sum(BLOCKS)
-        self.load_oracle_params({k: v for k, v in blob.items() if int(k[1:].split('.')[0]) < nb})
-        print('load pretrained weight', path, 'successfully')
+        self._load_backbone_weight(path, 'load pretrained weight')
 
 
 def reference_variable_map():

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from ._lib import BF16
 from .refinedet import RefineDet320
 from .voc_eval import EvaluateMixin
 
@@ -119,23 +119,13 @@ class LHRCNN(RefineDet320):
     # never run for, and its second training step sits 6-9 % off the oracle's loss where the exact engine holds 5e-2 (tests/test_gpu_lhrcnn.py).
     DEFAULT_ENGINE = 'f32'
     L2_AFTER = None
-    MOMENTUM_SLOT_SCOPE = 'rcnn/'           # the optimizer is created inside `with tf.variable_scope('rcnn')` (LH_RCNN.py:98, :171)
+    OPT_SLOT_SCOPE = 'rcnn/'                # the optimizer is created inside `with tf.variable_scope('rcnn')` (LH_RCNN.py:98, :171)
 
     def __init__(self, config, data_provider):
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider)
         self.data_shape = config['data_shape']
         self.num_classes = config['num_classes'] + 1          # background = LAST index
-        self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
         self.rpn_first_step = config['rpn_first_step']
         self.rcnn_first_step = config['rcnn_first_step']
         self.rpn_second_step = config['rpn_second_step']
@@ -145,32 +135,10 @@ class LHRCNN(RefineDet320):
         assert c == 3
         self._hw = (int(h), int(w))
         self.h, self.w = float(h - 1), float(w - 1)
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
         # 'bf16' (opt-in, end of round 3): the engine's bf16 kernels everywhere, the head's outputs widened to f32 in front of the loss / decode kernels.  Built from
         # launches that are each verified on MI355X (bf16 storage of the depthwise / crop kernels, the bf16 convolutions, the casts) but NOT yet run as a whole on
         # the GPU, and not put through the gradient-direction gate of DESIGN.md 5: f32 stays the default.
-        engine = config.get('compute_dtype', self.DEFAULT_ENGINE if config['mode'] == 'train' else 'f32')
-        # 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':
-            torch.cuda.set_device(self.dev)
+        self._set_engine(config.get('compute_dtype', self.DEFAULT_ENGINE if self.mode == 'train' else 'f32'))
         self.table = layer_table(self.num_classes)
         # what the engine sees: a separable layer is its pointwise 1x1 convolution (+ batch norm) behind a 'dw' plan entry; a dense layer is a 1x1 convolution with bias
         self.specs = [(n, 'vgg' if kind == 'dense' else 'conv', cin, cout, 1 if kind != 'conv' else kh, stride, 1, relu) for n, kind, cin, cout, kh, kw, stride, relu in self.table]
@@ -180,6 +148,7 @@ class LHRCNN(RefineDet320):
         for n, (kh, kw, cin) in self._sep.items():
             self.set_param(n + '.dw', torch.randn(kh, kw, cin, generator=g) * (2.0 / (kh * kw)) ** 0.5)
         self._build()
+        self.use_graph = False                                  # both optimizer ops and the R-CNN stage were never captured: this class launches eagerly
         self._warmup_setup(dict(config, f32_warmup_steps=config.get('f32_warmup_steps', 0)), data_provider, True)
         self._infer = None
 
@@ -260,7 +229,7 @@ class LHRCNN(RefineDet320):
             ops.cast_to_f32(st.logits, st.logits32)
             ops.cast_to_f32(st.pbbox, st.pbbox32)
 
-    def _loss_step(self):
+    def _loss_step(self, grad_scale):
         """RPN loss (gradients into the prediction tensors' gradient buffers), then the whole R-CNN stage forward AND backward down to d(rcnn_feat);
         -> (rpn data loss, rcnn data loss) as device scalars"""
         st, ws, N = self.loss, self.loss.ws, self.batch_size
@@ -270,7 +239,7 @@ class LHRCNN(RefineDet320):
         counts = ws['counts'].view(-1)
         ops.nms_batched(ws['pos_box'], cap * 4, ws['pos_score'], cap, 1, ws['pos_valid'], cap, 1, 1, cap, N, counts[3:], 8, 0, 0.7, ws['sel_pos'], 128, ws['cnt_pos'])
         ops.nms_batched(ws['neg_box'], cap * 4, ws['neg_score'], cap, 1, ws['neg_valid'], cap, 1, 1, cap, N, counts[4:], 8, 0, 0.7, ws['sel_neg'], 256, ws['cnt_neg'])
-        ops.lhrcnn_rpn_loss(self.anc, self.rpn_conf, self.rpn_bbox, self.gt, ws, self.num_classes, 1.0 / self.loss_divisor_batch, H, W, st.d_rpn_conf, st.d_rpn_bbox)
+        ops.lhrcnn_rpn_loss(self.anc, self.rpn_conf, self.rpn_bbox, self.gt, ws, self.num_classes, grad_scale, H, W, st.d_rpn_conf, st.d_rpn_bbox)
         f = self.feat
         ops.crop_and_resize_fwd(f.t, f.ld, N, f.H, f.W, f.C, ws['roi_box'], ws['roi_img'], CROP, st.roi, st.ldr)
         self._dense_fwd(st)
@@ -295,18 +264,16 @@ class LHRCNN(RefineDet320):
             ops.crop_and_resize_bwd(st.d_roi, st.ldr, N, f.H, f.W, f.C, ws['roi_box'], ws['roi_img'], CROP, f.g, f.ld)
         return ws['rpn_parts'][:, 3].sum() / self.batch_size, ws['rcnn_parts'].sum()
 
-    def _step_body(self):
-        self.G.zero_()
-        self._forward(True)
-        self._rpn_loss, self._rcnn_loss = self._loss_step()
+    def _loss(self, grad_scale):
+        self._rpn_loss, self._rcnn_loss = self._loss_step(grad_scale)
         if self.dist is not None:
             self.dist.layer_ready('roi_feat_dense')            # the three dense layers are the last segments of the flat gradient buffer
-        for name in self._backward_iter():
-            # a separable layer is complete when its depthwise filter gradient has been launched (the 'dw' entry follows its 1x1 layer in the backward plan)
-            if self.dist is not None:
-                base = name[:-3] if name.endswith('.dw') else name
-                if name.endswith('.dw') or base not in self._sep:
-                    self.dist.layer_ready(base)
+
+    def _layer_ready(self, name):
+        # a separable layer is complete when its depthwise filter gradient has been launched (the 'dw' entry follows its 1x1 layer in the backward plan)
+        base = name[:-3] if name.endswith('.dw') else name
+        if name.endswith('.dw') or base not in self._sep:
+            self.dist.layer_ready(base)
 
     def _reported(self, step):
         """the loss tf.case selects for the report (LH_RCNN.py:198-203, :471-478)"""
@@ -316,14 +283,8 @@ class LHRCNN(RefineDet320):
             return 'rcnn_loss'
         return 'rpn_loss' if step < self.rpn_second_step else 'rcnn_loss'
 
-    def _train_step_engine(self, lr):
-        """one step of BOTH optimizer ops (module docstring); returns the loss the schedule reports, data term + weight decay * l2 of that op's variables"""
-        if self.dist is not None:
-            self.dist.begin_step()
-        self._step_body()
-        self._eager_steps += 1
-        if self.dist is not None:
-            self.dist.finish_step()
+    def _optimizer_step(self, lr):
+        """BOTH optimizer ops (module docstring), each with the l2 of its own variables; the report is chosen by the step counter BEFORE this step"""
         b = self.pinfo[RCNN_FIRST + '.dw'][0]                   # backbone + RPN variables | 'rcnn' variables
         bf = self.DT == BF16
         nb = ops.sgd_blocks(b)
@@ -331,11 +292,13 @@ class LHRCNN(RefineDet320):
         ops.sgd_momentum(self.P[b:], self.Mom[b:], self.G[b:], lr, 0.9, self.weight_decay, 1.0, self.l2_partial[nb:], self.Pc[b:] if bf else None)
         ops.sum_f32(self.l2_partial[:nb], self.l2_sum)
         ops.sum_f32(self.l2_partial[nb:], self.l2_sum2)
-        self._fp_batch.run()
-        which = self._reported(self.global_step)
+        self._which = self._reported(self.global_step)
         self.global_step += 1
+
+    def _step_loss(self):
+        """the loss the schedule reports, data term + weight decay * l2 of that op's variables"""
         self.last_losses = (self._rpn_loss + self.weight_decay * self.l2_sum, self._rcnn_loss + self.weight_decay * self.l2_sum2)
-        return self.last_losses[0 if which == 'rpn_loss' else 1]
+        return self.last_losses[0 if self._which == 'rpn_loss' else 1]
 
     def _init_parameters(self, seed):
         super()._init_parameters(seed)
@@ -369,11 +332,7 @@ class LHRCNN(RefineDet320):
     test_images = EvaluateMixin.test_images
 
     def test_one_image(self, images):
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
+        self._stage_test_image(images)
         # reference quirk: `self.images` names the tensor after `/ 127.5 - 1` when test_one_image feeds it (LH_RCNN.py:68-69, :467): the fed pixels are used as they are
         self._forward(False, bool(self.config.get('test_normalise', False)))
         if self._infer is None:
@@ -427,16 +386,15 @@ class LHRCNN(RefineDet320):
                     out[f'{name}.{a}'] = f'{b}/{t}'
         return out
 
-    def _logical(self, name, buf):
+    def _to_tf(self, name, buf):
         v = self.get_param(name, buf)
         if name.endswith('.dw'):
             return np.ascontiguousarray(v.unsqueeze(-1).numpy())                      # [kh, kw, C, 1]
         if name.endswith('.w') and name[:-2] in ('roi_feat_dense', 'rcnn_pconf', 'rcnn_pbbox'):
             return np.ascontiguousarray(v.reshape(v.shape[0], v.shape[3]).t().numpy())   # [in, units]
-        return np.ascontiguousarray((v.permute(1, 2, 3, 0) if name.endswith('.w') else v).numpy())
+        return super()._to_tf(name, buf)
 
-    @staticmethod
-    def _from_tf(ours, arr):
+    def _from_tf(self, ours, arr):
         v = torch.from_numpy(np.asarray(arr))
         if ours.endswith('.dw'):
             return v.squeeze(-1)                                                      # [kh, kw, C, 1]
@@ -444,38 +402,9 @@ class LHRCNN(RefineDet320):
             return v.permute(3, 0, 1, 2).contiguous() if v.dim() == 4 else v.t().contiguous().reshape(v.shape[1], 1, 1, v.shape[0])
         return v
 
-    def load_tf_checkpoint(self, path):
-        """`saver.restore(sess, path)` from the files of a reference-trained model (or ours): weights, moving statistics, Momentum slots, global_step"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        for ours, tfname in self.reference_variable_map().items():
-            if ours in self.pinfo:
-                self.set_param(ours, self._from_tf(ours, reader.get_tensor(tfname)))      # KeyError = Saver's NotFoundError
-                slot = [k for k in names if k.endswith(tfname + '/Momentum')]
-                if slot:
-                    self.set_param(ours, self._from_tf(ours, reader.get_tensor(slot[0])), self.Mom)
-            else:
-                self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
-        if reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+    def _tf_is_backbone(self, ours, tfname):
+        return tfname.startswith('feature_extractor/') and ours in self.pinfo
 
     def load_pretraining_weight(self, path):
         """`self.pretraining_weight_saver.restore` (LH_RCNN.py:448-449, :511-513): the trainables of scope 'feature_extractor' from a tf.train.Saver checkpoint"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        for ours, tfname in self.reference_variable_map().items():
-            if tfname.startswith('feature_extractor/') and ours in self.pinfo:
-                v = torch.from_numpy(reader.get_tensor(tfname))                       # KeyError = Saver's NotFoundError
-                if ours.endswith('.dw'):
-                    v = v.squeeze(-1)
-                elif ours.endswith('.w'):
-                    v = v.permute(3, 0, 1, 2).contiguous()
-                self.set_param(ours, v)
-        self._refresh_operand_copies()
-        print('>> load pretraining weight', path, 'successfully')
+        self._load_backbone_weight(path, '>> load pretraining weight')

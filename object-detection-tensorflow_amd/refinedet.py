@@ -26,8 +26,7 @@ import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16
-from .base import DetectorBase
+from .base import DetectorBase, _Act
 from .warmup import F32Warmup
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -66,14 +65,6 @@ def layer_specs(num_classes):
     for l in range(4):
         head(f'odm{l + 1}', 256, num_classes)
     return s
-
-
-class _Act:
-    def __init__(self, name, N, H, W, C, ld, dtype, dev, vgg=False, alloc=True):
-        self.name, self.N, self.H, self.W, self.C, self.ld, self.vgg = name, N, H, W, C, ld, vgg
-        self.M = N * H * W
-        self.t = torch.zeros(self.M, ld, dtype=dtype, device=dev) if alloc else None
-        self.g = None
 
 
 class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
@@ -187,8 +178,9 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
         self.input = _Act('input', N, Hin, Win, 3, ops.pad_to(3, ch), dt, dev)
         self.plan, self.desc, self.z, self.bnsave, self.acts = [], {}, {}, {}, {'input': self.input}
         self._max_ws = self._max_z = self._max_scr = 0
-        self.use_graph = bool(self.config.get('use_graph', False))     # measured: replay is 6-7 % SLOWER than eager launches for these models
-        self._graph, self._graph_gt, self._eager_steps = None, None, 0
+        # config key 'use_graph' (default OFF).  Measured on MI355X at batch 32 bf16, same box, replay | eager: YOLOv2 13.4 | 12.55 ms, RefineDet320 21.4 | 20.1 ms
+        # -- the host keeps the queue full in eager mode (the step is not launch-bound) and a graph's kernel nodes cost more per node than queued launches
+        self.use_graph = bool(self.config.get('use_graph', False))
 
         def act(name, H_, W_, C_, vgg=False):
             a = _Act(name, N, H_, W_, C_, ops.pad_to(C_, ch), dt, dev, vgg)
@@ -545,45 +537,21 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
     def _make_loss(self, pad):
         return heads.RefineDetLoss(self.anc, self.batch_size, self.num_classes, pad, self.dev)
 
-    def _loss_step(self):
+    def _loss_step(self, grad_scale):
         """loss kernels on the predictions of _forward (gradients into self.loss.d_*) -> sum of the per-image losses / batch, a device scalar"""
-        parts = self.loss(self.arm_loc, self.arm_conf, self.odm_loc, self.odm_conf, self.gt, 1.0 / self.loss_divisor_batch)
+        parts = self.loss(self.arm_loc, self.arm_conf, self.odm_loc, self.odm_conf, self.gt, grad_scale)
         return parts[:, 6].sum() / self.batch_size
 
-    def _step_body(self):
-        self.G.zero_()
-        self._forward(True)
-        self._data_loss = self._loss_step()
-        for name in self._backward_iter():
-            # gradient segments of the all-reduce are the blocks before the first '.' (arm1, tcb3, ...); a block is final when its FIRST
-            # layer in creation order (.c1) has been processed -- backward walks a block's layers in reverse
-            if self.dist is not None and ('.' not in name or name.endswith('.c1')):
-                self.dist.layer_ready(name.split('.')[0])
+    def _loss(self, grad_scale):
+        self._data_loss = self._loss_step(grad_scale)
 
-    def _train_step_engine(self, lr):
-        """one MomentumOptimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor.
-        Single device, config key 'use_graph' (default OFF): after two eager steps (the library's lazily grown scratch buffers exist by then) forward +
-        loss + backward replay from ONE HIP graph; the optimizer launches stay outside (lr is a launch argument).  Measured on MI355X at batch 32 bf16,
-        same box, replay | eager: YOLOv2 13.4 | 12.55 ms, RefineDet320 21.4 | 20.1 ms -- the host keeps the queue full in eager mode (the step is not
-        launch-bound) and a graph's kernel nodes cost more per node than queued launches, so eager stays the default.  Data parallel: eager."""
-        if self.dist is not None:
-            self.dist.begin_step()
-        if self.use_graph and self.dist is None and self.dev.type == 'cuda' and self._eager_steps >= 2:
-            if self._graph is None or self._graph_gt is not self.gt:
-                self._graph = torch.cuda.CUDAGraph()
-                self._graph_gt = self.gt                       # the captured launches hold this buffer's pointer and pad length
-                with torch.cuda.graph(self._graph):
-                    self._step_body()
-            self._graph.replay()
-        else:
-            self._step_body()
-            self._eager_steps += 1
-        if self.dist is not None:
-            self.dist.finish_step()
-        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
-        ops.sum_f32(self.l2_partial, self.l2_sum)
-        self._fp_batch.run()
-        self.global_step += 1
+    def _layer_ready(self, name):
+        # gradient segments of the all-reduce are the blocks before the first '.' (arm1, tcb3, ...); a block is final when its FIRST
+        # layer in creation order (.c1) has been processed -- backward walks a block's layers in reverse
+        if '.' not in name or name.endswith('.c1'):
+            self.dist.layer_ready(name.split('.')[0])
+
+    def _step_loss(self):
         return self._data_loss + self.weight_decay * self.l2_sum      # RefineDet.py:180-184 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
@@ -603,7 +571,7 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
     # ------------------------------------------------------------------ checkpoints / data parallel
     # ------------------------------------------------------------------ the reference's variable names / tf.train.Saver files
     VGG_NAME_TYPOS = {'conv2_1.w': 'kenrel_conv2_1', 'conv3_1.b': 'bias_conv_3_1'}       # as spelt in the reference (RefineDet.py:251, :271; PFPNetR.py alike)
-    MOMENTUM_SLOT_SCOPE = 'inference/'      # the optimizer is created inside `with tf.variable_scope('inference')` (RefineDet.py:97, :176)
+    OPT_SLOT_SCOPE = 'inference/'           # the optimizer is created inside `with tf.variable_scope('inference')` (RefineDet.py:97, :176)
 
     def _tf_scope(self, name):
         """(variable scope, explicit layer name or None) of a layer of self.specs: default layer names (conv2d, conv2d_transpose, batch_normalization) are
@@ -637,36 +605,5 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
                 out[k] = 'feature_extractor/' + k
         return out
 
-    def export_tf_variables(self):
-        """what the reference's `tf.train.Saver()` would write: every global variable -- weights, moving statistics, global_step and the MomentumOptimizer slots"""
-        self._sync_from_twin()
-        out = OrderedDict()
-        for ours, tfname in self.reference_variable_map().items():
-            if ours in self.pinfo:
-                out[tfname] = self._logical(ours, self.P)
-                out[f'{self.MOMENTUM_SLOT_SCOPE}{tfname}/Momentum'] = self._logical(ours, self.Mom)
-            else:
-                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
-
-    def load_tf_checkpoint(self, path):
-        """`saver.restore(sess, path)` from the files of a reference-trained model (or ours)"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        for ours, tfname in self.reference_variable_map().items():
-            if ours in self.pinfo:
-                v = torch.from_numpy(reader.get_tensor(tfname))                 # KeyError = Saver's NotFoundError
-                self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-                slot = [k for k in names if k.endswith(tfname + '/Momentum')]
-                if slot:
-                    mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                    self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
-            else:
-                self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
-        if reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+    def tf_variable_map(self):
+        return OrderedDict(self.reference_variable_map())

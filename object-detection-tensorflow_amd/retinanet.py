@@ -30,7 +30,6 @@ import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16
 from .base import DetectorBase, _Act
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -410,20 +409,9 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor"""
         if self.is_pretraining:
             return self._pretraining_step(lr)
-        if self.dist is not None:
-            self.dist.begin_step()
-        self.G.zero_()
-        self._forward(True)
-        self._loss(1.0 / self.loss_divisor_batch)
-        for name in self._backward_iter():
-            if self.dist is not None:
-                self.dist.layer_ready(name)
-        if self.dist is not None:
-            self.dist.finish_step()
-        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
-        ops.sum_f32(self.l2_partial, self.l2_sum)
-        self._fp_batch.run()
-        self.global_step += 1
+        return self._train_step_engine(lr)
+
+    def _step_loss(self):
         return self.loss_parts.sum() / self.batch_size + self.weight_decay * self.l2_sum          # RetinaNet.py:205-213
 
     # ------------------------------------------------------------------ public: inference
@@ -452,41 +440,15 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         return super().evaluate(num_images, generator, **kw)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def export_tf_variables(self):
-        """what the reference's detection `tf.train.Saver()` (RetinaNet.py:553-557) writes: every variable of the graph under its name
-        (reference_variable_map), global_step, and the momentum slots, created inside the 'inference' scope (:172, :206)"""
-        out = OrderedDict()
-        for tfname, ours in reference_variable_map(self.block_list).items():
-            if ours in self.pinfo:
-                out[tfname] = self._logical(ours, self.P)
-                out[f'inference/{tfname}/Momentum'] = self._logical(ours, self.Mom)
-            else:
-                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
+    OPT_SLOT_SCOPE = 'inference/'           # the momentum slots are created inside the 'inference' scope (RetinaNet.py:172, :206)
+    TF_STATS_OPTIONAL = True                # a pre-training checkpoint holds no moving statistics (RetinaNet.py:548-551)
 
-    def load_tf_checkpoint(self, path, backbone_only=False):
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        nb = 1 + 4 * sum(self.block_list)
-        for tfname, ours in reference_variable_map(self.block_list).items():
-            if backbone_only and int(ours[1:].split('.')[0]) >= nb:
-                continue
-            if ours in self.sinfo and not reader.has_tensor(tfname):
-                continue                                # a pre-training checkpoint holds no moving statistics (RetinaNet.py:548-551)
-            v = torch.from_numpy(reader.get_tensor(tfname))
-            if ours in self.sinfo:
-                self.stat(ours).copy_(v.to(self.dev))
-                continue
-            self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-            slot = [k for k in names if k.endswith(tfname + '/Momentum')]
-            if slot and not backbone_only:
-                mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
-        if not backbone_only and reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+    def tf_variable_map(self):
+        """the variables of the reference's detection `tf.train.Saver()` (RetinaNet.py:553-557)"""
+        return OrderedDict((ours, tfname) for tfname, ours in reference_variable_map(self.block_list).items())
+
+    def _tf_is_backbone(self, ours, tfname):
+        return int(ours[1:].split('.')[0]) < 1 + 4 * sum(self.block_list)          # stem + units, their moving statistics included when the file has them
 
     def save_weight(self, mode, path):
         """RetinaNet.py:521-531.  config['checkpoint_format'] = 'tf' writes tf.train.Saver files (tf_checkpoint.py)."""
@@ -495,14 +457,7 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
     def load_pretraining_weight(self, path):
         """RetinaNet.py:537-539 restores the 'feature_extractor' variables saved by the pre-training graph: here the backbone layers
         (stem + units) of a saved file"""
-        if os.path.exists(str(path) + '.index'):
-            self.load_tf_checkpoint(path, backbone_only=True)
-            print('load pretraining weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)['params']
-        nb = 1 + 4 * sum(self.block_list)
-        self.load_oracle_params({k: v for k, v in blob.items() if int(k[1:].split('.')[0]) < nb})
-        print('load pretraining weight', path, 'successfully')
+        self._load_backbone_weight(path, 'load pretraining weight')
 
     def attach_data_parallel(self, group=None, bucket_mb=25, grad_dtype='f32', force_collectives=False, collective='torch'):
         if self.is_pretraining:
@@ -576,10 +531,8 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         self._forward(True)
         for _ in self._backward_iter():
             pass
-        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
-        ops.sum_f32(self.l2_partial, self.l2_sum)
+        self._optimizer_step(lr)
         self._fp_batch.run()
-        self.global_step += 1
         # :128-130 compares pred (int64) with labels (int32), which TF 1.x refuses as written: the evident intent, mean(pred == label), is built
         self.last_accuracy = self.correct.mean()
         return self.ce.sum() / self.batch_size + self.weight_decay * self.l2_sum
@@ -671,7 +624,7 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
     def export_pretraining_tf_variables(self):
         """what the pre-training `tf.train.Saver(tf.trainable_variables('feature_extractor'))` (RetinaNet.py:548-551) writes: the kernels, biases,
         gammas and betas of l0 .. l64 under the detection graph's names -- no moving statistics, no momentum slots, no global_step"""
-        return OrderedDict((tfname, self._logical(ours, self.P)) for tfname, ours in reference_variable_map(self.block_list).items() if ours in self.pinfo)
+        return OrderedDict((tfname, self._to_tf(ours, self.P)) for ours, tfname in self.tf_variable_map().items() if ours in self.pinfo)
 
     def _save_pretraining_weight(self, mode, path):
         """RetinaNet.py:509-519.  'tf': exactly the trainables of the pre-training Saver; torch: the same trainables plus momentum and global_step

@@ -1154,51 +1154,11 @@ class SSD300(BatchedInference, F32Warmup, DetectorBase):
         t.launch_own(self.nms_iou_threshold)
 
     # ------------------------------------------------------------------ checkpoints
+    OPT_SLOT_SCOPE = 'inference/'           # the MomentumOptimizer slots are created inside the 'inference' scope (SSD300.py:104, :149)
+
     def tf_variable_map(self):
-        return reference_variable_map(self.EXTRA_SEQ, self.NH)
-
-    def _logical(self, name, buf):
-        """parameter `name` out of a flat buffer (P or Mom) in TensorFlow's layout: kernels HWIO, un-padded"""
-        v = self.param(name, buf).detach().cpu()
-        if name.endswith('.w'):
-            v = v[..., : self.convs[name[:-2]].cin].permute(1, 2, 3, 0)
-        return np.ascontiguousarray(v.numpy())
-
-    def export_tf_variables(self):
-        """what the reference's `tf.train.Saver()` (SSD300.py:464-466) would write: every global variable -- weights, BN
-        moving statistics, global_step and the MomentumOptimizer slots, which are created inside the 'inference' scope
-        (:104, :149) and therefore named inference/<variable>/Momentum."""
-        self._sync_from_twin()
-        out = OrderedDict()
-        for tfname, ours in self.tf_variable_map().items():
-            if ours in self.pinfo:
-                out[tfname] = self._logical(ours, self.P)
-                out[f'inference/{tfname}/Momentum'] = self._logical(ours, self.Mom)
-            else:
-                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
-
-    def load_tf_checkpoint(self, path):
-        """`saver.restore(sess, path)` (SSD300.py:502-504) from the files of a reference-trained model (or ours)."""
-        from .tf_checkpoint import NewCheckpointReader
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        for tfname, ours in self.tf_variable_map().items():
-            if ours in self.pinfo:
-                v = torch.from_numpy(reader.get_tensor(tfname))                 # KeyError = Saver's NotFoundError
-                self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-                slot = [k for k in names if k.endswith(tfname + '/Momentum')]
-                if slot:
-                    mv = torch.from_numpy(reader.get_tensor(slot[0]))
-                    self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
-            else:
-                self.stat(ours).copy_(torch.from_numpy(reader.get_tensor(tfname)).to(self.dev))
-        if reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+        """the global variables of the reference's `tf.train.Saver()` (SSD300.py:464-466, restored at :502-504)"""
+        return OrderedDict((ours, tfname) for tfname, ours in reference_variable_map(self.EXTRA_SEQ, self.NH).items())
 
     # ------------------------------------------------------------------ data parallel
     def attach_data_parallel(self, group=None, bucket_mb=25, sync_bn=False, grad_dtype='f32', force_collectives=False, collective='torch'):

@@ -14,11 +14,9 @@ The graph engine is refinedet.RefineDet320's (per-activation gradient buffers, t
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
-from . import heads, ops
-from ._lib import BF16, F32, F32X3
+from . import heads
 from .refinedet import RefineDet320
 from .voc_eval import EvaluateMixin
 
@@ -68,24 +66,13 @@ class YOLOv2(RefineDet320):
 
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
-        assert config['mode'] in ['train', 'test']
-        assert config['data_format'] in ['channels_first', 'channels_last']
-        self.config = config
-        self.data_provider = data_provider
+        self._prologue(config, data_provider)
         self.data_shape = config['data_shape']
-        self.num_classes = config['num_classes']
-        self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']
-        self.data_format = config['data_format']
-        self.mode = config['mode']
-        self.batch_size = config['batch_size'] if config['mode'] == 'train' else 1
         self.coord_sacle = config['coord_scale']                # (sic, YOLOv2.py:25)
         self.noobj_scale = config['noobj_scale']
         self.obj_scale = config['obj_scale']
         self.class_scale = config['class_scale']
-        self.nms_score_threshold = config['nms_score_threshold']
-        self.nms_max_boxes = config['nms_max_boxes']
-        self.nms_iou_threshold = config['nms_iou_threshold']
         self.rescore_confidence = config['rescore_confidence']
         self.num_priors = len(config['priors'])
         self.priors_flat = [float(v) for hw in config['priors'] for v in hw]
@@ -93,35 +80,13 @@ class YOLOv2(RefineDet320):
         h, w, c = self.data_shape if self.data_format == 'channels_last' else (self.data_shape[1], self.data_shape[2], self.data_shape[0])
         assert c == 3 and h % 32 == 0 and w % 32 == 0, "YOLOv2 needs an input that is a multiple of 32 (five 2x2 pools)"
         self._hw = (h, w)
-        if self.mode == 'train':
-            self.num_train = data_provider['num_train']
-            self.num_val = data_provider['num_val']
-            self.train_generator = data_provider['train_generator']
-            if isinstance(self.train_generator, tuple) and len(self.train_generator) == 2:
-                self.train_initializer, self.train_iterator = self.train_generator
-            else:
-                self.train_initializer, self.train_iterator = None, self.train_generator
-            if data_provider.get('val_generator') is not None:
-                self.val_generator = data_provider['val_generator']
-        self.verbose = bool(config.get('verbose', True))
-        self.dev = torch.device(config.get('device', 'cuda:0'))
-        engine = config.get('compute_dtype', self.DEFAULT_ENGINE if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32')
-        # 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is faster: include/odtk.h)
-        self.DT = {'bf16': BF16, 'f32': F32, 'f32x3': F32}[engine]
-        self.CDT = F32X3 if engine == 'f32x3' else self.DT
-        self.tdt = torch.bfloat16 if self.DT == BF16 else torch.float32
-        self.chunk = ops.chunk(self.DT)
-        self.global_step = 0
-        self.dist = None
-        self.loss_divisor_batch = self.batch_size
-        if self.dev.type == 'cuda':
-            torch.cuda.set_device(self.dev)
+        self._set_engine(config.get('compute_dtype', self.DEFAULT_ENGINE if (self.dev.type == 'cuda' and self.mode == 'train') else 'f32'))
         self.specs = layer_specs(self.num_classes, self.num_priors)
         self._init_parameters(int(config.get('seed', 0)))
         self._build()
         self._warmup_setup(config, data_provider, 'compute_dtype' in config)
 
-    MOMENTUM_SLOT_SCOPE = ''                # the optimizer is created outside every variable scope (YOLOv2.py:168)
+    OPT_SLOT_SCOPE = ''                     # the optimizer is created outside every variable scope (YOLOv2.py:168)
 
     def reference_variable_map(self):
         return reference_variable_map()
@@ -157,19 +122,15 @@ class YOLOv2(RefineDet320):
         return heads.YOLOv2Loss(self.batch_size, H, W, self.num_priors, self.num_classes, self.priors_flat,
                                 (self.coord_sacle, self.noobj_scale, self.obj_scale, self.class_scale), self.dev)
 
-    def _loss_step(self):
-        parts = self.loss(self.pred, self.gt, 1.0 / self.loss_divisor_batch, STRIDE)
+    def _loss_step(self, grad_scale):
+        parts = self.loss(self.pred, self.gt, grad_scale, STRIDE)
         return parts[:, 4].sum() / self.batch_size
 
     NATIVE_TEST_IMAGES = False              # the batched tail of refinedet.RefineDet320 is not this class's: test_images is the loop over test_one_image
     test_images = EvaluateMixin.test_images
 
     def test_one_image(self, images):
-        images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
-        if self.data_format == 'channels_first' and images.shape[1] == 3:
-            images = images.permute(0, 2, 3, 1)
-        assert self.batch_size == 1 and tuple(images.shape) == tuple(self.images.shape), images.shape
-        self.images.copy_(images)
+        self._stage_test_image(images)
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
         H, W = self.grid
         scores, bbox, cid = heads.yolov2_detect(self.pred[0].view(H, W, self.num_priors, self.num_classes + 5), self.priors_flat,
@@ -178,14 +139,4 @@ class YOLOv2(RefineDet320):
 
     def load_pretraining_weight(self, path):
         """`self.pretraining_weight_saver.restore` (YOLOv2.py:206-208, :355-357): the trainables of scope 'backone' from a tf.train.Saver checkpoint"""
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()                                   # weights are loaded: the run does not start from random initialisation
-        from .tf_checkpoint import NewCheckpointReader
-        reader = NewCheckpointReader(str(path))
-        names = reference_variable_map()
-        for ours in self.pinfo:
-            if ours.startswith('b'):
-                v = torch.from_numpy(reader.get_tensor(names[ours]))          # KeyError = Saver's NotFoundError
-                self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-        self._refresh_operand_copies()
-        print('>> load pretraining weight', path, 'successfully')
+        self._load_backbone_weight(path, '>> load pretraining weight')

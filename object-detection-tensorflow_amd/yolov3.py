@@ -23,14 +23,12 @@ data-parallel gradient buckets of dist.py rely on).
 from __future__ import annotations
 
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import heads, ops
-from ._lib import BF16
 from .base import DetectorBase, _Act
 from .warmup import F32Warmup
 
@@ -63,8 +61,8 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
         self._set_engine(config.get('compute_dtype', 'f32x3' if (self.dev.type == 'cuda' and self.mode == 'train') else 'bf16'))
         h, w, c = self.data_shape
         assert c == 3 and h % 32 == 0 and w % 32 == 0, "YOLOv3 needs an input that is a multiple of 32 (five stride-2 stages)"
+        # measured: ~1 000 dependent launches of 5-25 us each -- this class's step is launch-bound, replay is the default
         self.use_graph = bool(config.get('use_graph', True))
-        self._graph, self._graph_gt, self._eager_steps = None, None, 0
         self.sync_bn = None
         self.specs = layer_specs(self.num_classes, self.num_priors)
         self._init_parameters(int(config.get('seed', 0)))
@@ -261,37 +259,10 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
                 ops.upsample2x_bwd(dcat[:, bottom.C:], y.ld, self.grad_of(lat), lat.ld, lat.N, lat.H, lat.W, lat.C, False)
 
     # ------------------------------------------------------------------ public: training
-    def _step_body(self):
-        self.G.zero_()
-        self._forward(True)
-        self._loss(0.5 / self.loss_divisor_batch)              # d(.5 * mean_i loss_i)
-        for name in self._backward_iter():
-            if self.dist is not None:
-                self.dist.layer_ready(name)
+    def _loss_scale(self):
+        return 0.5 / self.loss_divisor_batch                   # d(.5 * mean_i loss_i)
 
-    def _train_step_engine(self, lr):
-        """one optimizer step on the batch of set_batch(); returns the loss (data + L2) as a 1-element device tensor.
-        Single device: after two eager steps (the library's lazily grown scratch buffers exist by then) forward + loss + backward
-        replay from ONE HIP graph -- ~1 000 dependent launches of 5-25 us each leave the queue without host round trips; the
-        optimizer launches stay outside (lr is a launch argument).  Data parallel / sync-BN: eager (collectives inside the step)."""
-        if self.dist is not None:
-            self.dist.begin_step()
-        if self.use_graph and self.dist is None and self._eager_steps >= 2:
-            if self._graph is None or self._graph_gt is not self.gt:
-                self._graph = torch.cuda.CUDAGraph()
-                self._graph_gt = self.gt                       # the captured launches hold this buffer's pointer and pad length
-                with torch.cuda.graph(self._graph):
-                    self._step_body()
-            self._graph.replay()
-        else:
-            self._step_body()
-            self._eager_steps += 1
-        if self.dist is not None:
-            self.dist.finish_step()
-        ops.sgd_momentum(self.P, self.Mom, self.G, lr, 0.9, self.weight_decay, 1.0, self.l2_partial, self.Pc if self.DT == BF16 else None)
-        ops.sum_f32(self.l2_partial, self.l2_sum)
-        self._fp_batch.run()
-        self.global_step += 1
+    def _step_loss(self):
         return 0.5 * self.loss_parts[:, 4].mean() + self.weight_decay * self.l2_sum        # YOLOv3.py:311-315 (pre-update weights)
 
     # ------------------------------------------------------------------ public: inference
@@ -313,53 +284,19 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
         t.launch_own(self.nms_iou_threshold)
 
     # ------------------------------------------------------------------ checkpoints / data parallel
-    def export_tf_variables(self):
-        """what the reference's `tf.train.Saver()` (YOLOv3.py:377-381) writes: every variable of its graph under its name
-        (reference_variable_map), global_step, and the momentum slots `<variable>/Momentum` (the optimizer is created outside any
-        variable scope, :312)"""
-        self._sync_from_twin()
-        out = OrderedDict()
-        for tfname, ours in reference_variable_map().items():
-            if ours in self.pinfo:
-                out[tfname] = self._logical(ours, self.P)
-                out[tfname + '/Momentum'] = self._logical(ours, self.Mom)
-            else:
-                out[tfname] = self.stat(ours).detach().cpu().numpy().copy()
-        out['global_step'] = np.asarray(self.global_step, dtype=np.int32)
-        return out
+    def tf_variable_map(self):
+        """the variables of the reference's `tf.train.Saver()` (YOLOv3.py:377-381); the momentum slots are `<variable>/Momentum`: the optimizer is
+        created outside any variable scope (:312)"""
+        return OrderedDict((ours, tfname) for tfname, ours in reference_variable_map().items())
 
-    def load_tf_checkpoint(self, path, backbone_trainables_only=False):
-        """`saver.restore(sess, path)` from tf.train.Saver files (ours or the reference's); backbone_trainables_only: what
-        `pretraining_weight_saver` restores (YOLOv3.py:377-378, :480-482: the trainable variables under 'backone')"""
-        from .tf_checkpoint import NewCheckpointReader
-        if getattr(self, 'f32_warmup_steps', 0):
-            self.cancel_warmup()
-        reader = NewCheckpointReader(str(path))
-        names = reader.get_variable_to_shape_map()
-        for tfname, ours in reference_variable_map().items():
-            if backbone_trainables_only and (not tfname.startswith('backone') or ours in self.sinfo):
-                continue
-            v = torch.from_numpy(reader.get_tensor(tfname))                     # KeyError = Saver's NotFoundError
-            if ours in self.sinfo:
-                self.stat(ours).copy_(v.to(self.dev))
-                continue
-            self.set_param(ours, v.permute(3, 0, 1, 2).contiguous() if ours.endswith('.w') else v)
-            if not backbone_trainables_only and tfname + '/Momentum' in names:
-                mv = torch.from_numpy(reader.get_tensor(tfname + '/Momentum'))
-                self.set_param(ours, mv.permute(3, 0, 1, 2) if ours.endswith('.w') else mv, self.Mom)
-        if not backbone_trainables_only and reader.has_tensor('global_step'):
-            self.global_step = int(reader.get_tensor('global_step'))
-        self._refresh_operand_copies()
+    def load_tf_checkpoint(self, path, backbone_trainables_only=False, backbone_only=False):
+        """backbone_trainables_only (this class's own keyword for backbone_only): what `pretraining_weight_saver` restores (YOLOv3.py:377-378,
+        :480-482: the trainable variables under 'backone')"""
+        super().load_tf_checkpoint(path, backbone_only or backbone_trainables_only)
 
     def load_pretraining_weight(self, path):
         """YOLOv3.py:480-482 restores the trainable 'backone' variables: here the c0 .. c51 entries of a saved file"""
-        if os.path.exists(str(path) + '.index'):
-            self.load_tf_checkpoint(path, backbone_trainables_only=True)
-            print('load pretraining weight', path, 'successfully')
-            return
-        blob = torch.load(path, map_location='cpu', weights_only=True)['params']
-        self.load_oracle_params({k: v for k, v in blob.items() if int(k[1:].split('.')[0]) < 52 and k in self.pinfo})
-        print('load pretraining weight', path, 'successfully')
+        self._load_backbone_weight(path, 'load pretraining weight')
 
     def attach_data_parallel(self, group=None, bucket_mb=25, sync_bn=False, grad_dtype='f32', force_collectives=False, collective='torch'):
         """images sharded over ranks (one process per GPU); gradients summed with the bucketed RCCL all-reduce of dist.py,

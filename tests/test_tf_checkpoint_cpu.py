@@ -359,7 +359,7 @@ def test_engine_models_reference_names_and_saver_round_trip(kind, tmp_path):
         assert set(tf_vars) <= set(shapes)                                   # every variable of the reference's graph is in the file ...
         for n, meta in tf_vars.items():                                     # ... with the shape the reference's graph gives it (at this input size)
             assert list(shapes[n]) == meta['shape'], (n, shapes[n], meta['shape'])
-        slot = m.MOMENTUM_SLOT_SCOPE + names[m.specs[-1][0] + '.w'] + '/Momentum'
+        slot = m.OPT_SLOT_SCOPE + names[m.specs[-1][0] + '.w'] + '/Momentum'
         assert slot in shapes and int(reader.get_tensor('global_step')) == 37
         m2 = make(2)
         assert not torch.equal(m2.P, m.P)
@@ -518,7 +518,7 @@ def test_lhrcnn_reference_names_and_saver_round_trip(tmp_path):
         for n, meta in tf_vars.items():
             assert list(shapes[n]) == meta['shape'], (n, shapes[n], meta['shape'])
         scope = json.load(open(os.path.join(here, 'golden', 'optimizer_scopes.json')))['LHRCNN']       # recorded on the reference's own class
-        assert scope == 'rcnn' and m.MOMENTUM_SLOT_SCOPE == scope + '/'
+        assert scope == 'rcnn' and m.OPT_SLOT_SCOPE == scope + '/'
         for ours in ('conv1.w', 'stage3_sconv4.dw', 'rpn_pbbox.gamma', 'state5_conv2_2.w', 'roi_feat_dense.w', 'rcnn_pbbox.b'):
             assert 'rcnn/' + names[ours] + '/Momentum' in shapes, ours
         assert int(reader.get_tensor('global_step')) == 41
@@ -530,3 +530,156 @@ def test_lhrcnn_reference_names_and_saver_round_trip(tmp_path):
             if k.endswith('.b') and k[:-2] in m._sep:
                 continue                                                      # the engine's inert bias of a separable layer: not a variable of the graph
             assert torch.equal(m2.get_param(k), m.get_param(k)) and torch.equal(m2.get_param(k, m2.Mom), m.get_param(k, m.Mom)), k
+
+
+# ---------------------------------------------------------------------- the shared Saver path of base.DetectorBase
+# every class at batch 2, the smallest input and the engine tools/state_fingerprint.py builds it at (its CASES), on the CPU stand-in of the library
+SAVER_CASES = ['ssd300', 'ssd512', 'yolov3', 'retinanet', 'fcos', 'centernet', 'refinedet', 'pfpnet', 'yolov2', 'lhrcnn']
+# the parameters each class's backbone restore takes, written down independently of the class's own predicate
+BACKBONE = {'yolov3': lambda m, k: int(k[1:].split('.')[0]) < 52, 'retinanet': lambda m, k: int(k[1:].split('.')[0]) < 65,
+            'fcos': lambda m, k: int(k[1:].split('.')[0]) < 65, 'centernet': lambda m, k: int(k[1:].split('.')[0]) < 50,
+            'yolov2': lambda m, k: k.startswith('b'), 'lhrcnn': lambda m, k: m.reference_variable_map().get(k, '').startswith('feature_extractor/')}
+
+
+@contextlib.contextmanager
+def _cpu_models(case):
+    """-> make(): a fresh train-mode model of `case` under the mocked launches"""
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    for p in (here, os.path.join(os.path.dirname(here), 'tools')):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import mock_ops
+    import state_fingerprint as F
+    kind, size, engine = F.CASES[case]
+    tables = contextlib.nullcontext()
+    if case == 'ssd512':
+        from oracle import ssd512_ref
+        tables = ssd512_ref.tables()
+    with mock_ops.installed(), tables:
+        yield lambda: F.build(kind, size, engine, 'cpu')[0]
+
+
+def _trained_look(m, seed):
+    """parameters, optimizer buffers and statistics no fresh model has"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    m.P.mul_(1.0 + torch.rand(m.P.shape, generator=g))
+    for name in m.OPT_BUFFERS:
+        getattr(m, name).copy_(torch.rand(m.P.shape, generator=g) * 1e-3)
+    if m.sinfo:
+        m.S.copy_(torch.rand(m.S.shape, generator=g) + 0.5)
+    m._refresh_operand_copies()
+
+
+def _saver_file_without_slots(m, prefix, statistics=True):
+    out = {k: v for k, v in m.export_tf_variables().items() if not k.endswith(tuple('/' + s for s in m.OPT_SLOTS))}
+    assert len(out) < len(m.export_tf_variables())
+    if not statistics:
+        out = {k: v for k, v in out.items() if not k.endswith(('/moving_mean', '/moving_variance'))}
+    T.write_bundle(prefix, out)
+    return out
+
+
+@pytest.mark.parametrize('case', SAVER_CASES)
+def test_saver_file_without_slots_leaves_the_optimizer_buffers(case, tmp_path):
+    """a file of export_tf_variables WITHOUT the optimizer slots loads: the parameters are the file's, the optimizer buffers stay bit for bit, and only
+    CenterNet -- whose global_step drives Adam's bias correction -- warns, once"""
+    import warnings
+    import torch
+    with _cpu_models(case) as make:
+        m = make()
+        _trained_look(m, 1)
+        m.global_step = 6
+        prefix = str(tmp_path / 'noslots')
+        _saver_file_without_slots(m, prefix)
+        m2 = make()
+        _trained_look(m2, 2)
+        before = {n: getattr(m2, n).clone() for n in m2.OPT_BUFFERS}
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter('always')
+            m2.load_tf_checkpoint(prefix)
+        runtime = [w for w in caught if issubclass(w.category, RuntimeWarning)]
+        assert len(runtime) == (1 if case == 'centernet' else 0), [str(w.message) for w in runtime]
+        if runtime:
+            assert 'Adam slot variables not in the checkpoint' in str(runtime[0].message) and 'global_step = 6' in str(runtime[0].message)
+        assert all(torch.equal(getattr(m2, n), before[n]) for n in m2.OPT_BUFFERS) and m2.global_step == 6
+        names = m.tf_variable_map()
+        assert all(torch.equal(m2.get_param(k), m.get_param(k)) for k in m.pinfo if k in names)
+        assert all(torch.equal(m2.stat(k), m.stat(k)) for k in m.sinfo)
+
+
+@pytest.mark.parametrize('case', sorted(BACKBONE))
+def test_backbone_restore_takes_the_backbone_parameters_only(case, tmp_path):
+    """_load_backbone_weight: every backbone parameter is the file's; every other parameter, every moving statistic, the optimizer buffers and global_step
+    stay bit for bit.  RetinaNet's file is what the reference's pre-training Saver writes, trainables only (RetinaNet.py:548-551): from a DETECTION file
+    this class also takes the backbone's moving statistics, which tests/test_gpu_retinanet_model.py pins"""
+    import torch
+    with _cpu_models(case) as make:
+        m = make()
+        _trained_look(m, 3)
+        m.global_step = 9
+        prefix = str(tmp_path / 'backbone')
+        _saver_file_without_slots(m, prefix, statistics=case != 'retinanet')
+        m2 = make()
+        _trained_look(m2, 4)
+        before = {k: m2.get_param(k) for k in m2.pinfo}
+        state = {n: getattr(m2, n).clone() for n in m2.OPT_BUFFERS + (('S',) if m2.sinfo else ())}
+        m2._load_backbone_weight(prefix, 'load')
+        inside = [k for k in m2.pinfo if BACKBONE[case](m2, k)]
+        assert 0 < len(inside) < len(m2.pinfo)
+        for k in m2.pinfo:
+            assert torch.equal(m2.get_param(k), m.get_param(k) if k in inside else before[k]), k
+        assert all(torch.equal(getattr(m2, n), v) for n, v in state.items()) and m2.global_step == 0
+
+
+def test_centernet_torch_checkpoint_through_the_base_load_weight(tmp_path):
+    """CenterNet's torch file (keys 'adam_m', 'adam_v') restores both moments through DetectorBase.load_weight; a file of another layout leaves them
+    untouched and says so"""
+    import torch
+    with _cpu_models('centernet') as make:
+        m = make()
+        _trained_look(m, 5)
+        m.global_step = 3
+        path = str(tmp_path / 'ck' / 'centernet')
+        m.save_weight('latest', path)
+        blob = torch.load(path + '-3', map_location='cpu', weights_only=True)
+        assert {'adam_m', 'adam_v', 'params', 'layout', 'global_step'} <= set(blob)
+        m2 = make()
+        m2.load_weight(path + '-3')
+        assert torch.equal(m2.M1, m.M1) and torch.equal(m2.M2, m.M2) and torch.equal(m2.P, m.P) and m2.global_step == 3
+        blob['layout'] = {k: v for k, v in list(blob['layout'].items())[:-1]}
+        torch.save(blob, path + '-other')
+        m3 = make()
+        _trained_look(m3, 6)
+        m1, m2_ = m3.M1.clone(), m3.M2.clone()
+        with pytest.warns(RuntimeWarning, match='Adam moments NOT restored'):
+            m3.load_weight(path + '-other')
+        assert torch.equal(m3.M1, m1) and torch.equal(m3.M2, m2_) and torch.equal(m3.P, m.P) and m3.global_step == 3
+
+
+def test_lhrcnn_kernel_layouts_survive_to_tf_and_back():
+    """LHRCNN._to_tf -> _from_tf: depthwise kernels ([kh, kw, C] <-> [kh, kw, C, 1]), dense kernels ([units, 1, 1, in] <-> [in, units]) and the
+    convolutions come back bit for bit, out of P and out of the momentum buffer"""
+    import torch
+    with _cpu_models('lhrcnn') as make:
+        m = make()
+        _trained_look(m, 7)
+        seen = set()
+        for k in m.reference_variable_map():
+            if k not in m.pinfo:
+                continue
+            for buf in (m.P, m.Mom):
+                tf = m._to_tf(k, buf)
+                assert torch.equal(m._from_tf(k, tf), m.get_param(k, buf)), k
+            v = m.get_param(k)
+            if k.endswith('.dw'):
+                assert tf.shape == tuple(v.shape) + (1,)
+                seen.add('dw')
+            elif k.endswith('.w') and k[:-2] in ('roi_feat_dense', 'rcnn_pconf', 'rcnn_pbbox'):
+                assert tf.shape == (v.shape[3], v.shape[0])
+                seen.add('dense')
+            elif k.endswith('.w'):
+                assert tf.shape == (v.shape[1], v.shape[2], v.shape[3], v.shape[0])
+                seen.add('conv')
+        assert seen == {'dw', 'dense', 'conv'}

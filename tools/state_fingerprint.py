@@ -15,6 +15,11 @@ so the second step crosses the hand-over from the f32 twin):
   checkpoint ... key set and tensor hashes of the torch file save_weight wrote, re-read
   loaded ....... SHA-256 of P and the optimizer buffers of a FRESH model after load_weight of that file, and its global_step
   detections ... SHA-256 of the three arrays test_one_image returns from a test-mode model (f32 engine) loaded with those parameters
+  tf_loaded .... the same model saved with checkpoint_format='tf' (tf.train.Saver files) and load_weight of that prefix into a FRESH model: SHA-256 of P,
+                 the optimizer buffers and S, and its global_step
+  backbone_loaded  a FRESH model restored from that prefix through load_pretraining_weight / load_pretrained_weight (the classes that have one): SHA-256
+                 of P and of the optimizer buffers, which must be the fresh model's own, and global_step
+  graph_steps .. yolov3 and refinedet on the GPU: a model built with use_graph=True after FIVE steps (two eager, the capture, two replays): loss and state
 The file keeps the first 64 bits of every hash.  Without --full the long tables -- the hashes of every array of export_tf_variables() and of every
 entry of the checkpoint's 'params' and 'layout' -- are folded into {'n': count, 'sha': SHA-256 over the sorted 'name:hash' lines}, so that a file stays a page long.
 """
@@ -89,6 +94,13 @@ def state(m):
     return out
 
 
+def loaded_state(m):
+    out = {n: sha(getattr(m, n)) for n in ('P',) + opt_buffers(m)}
+    if hasattr(m, 'S'):
+        out['S'] = sha(m.S)
+    return out
+
+
 def hash_tree(v):
     import torch
     if isinstance(v, torch.Tensor):
@@ -119,7 +131,27 @@ def fingerprint(case, device):
         fresh = build(kind, size, engine, device)[0]
         fresh.load_weight(path)
         rec['loaded'] = dict({n: sha(getattr(fresh, n)) for n in ('P',) + opt_buffers(fresh)}, global_step=int(fresh.global_step))
+        m.config['checkpoint_format'] = 'tf'
+        tf_prefix = os.path.join(tmp, 'saver')
+        m.save_weight('latest', tf_prefix)
+        tf_path = tf_prefix + '-' + str(m.global_step)
+        fresh = build(kind, size, engine, device)[0]
+        fresh.load_weight(tf_path)
+        rec['tf_loaded'] = dict(loaded_state(fresh), global_step=int(fresh.global_step))
+        fresh = build(kind, size, engine, device)[0]
+        restore = getattr(fresh, 'load_pretraining_weight', None) or getattr(fresh, 'load_pretrained_weight', None)
+        if restore is not None:
+            untouched = {n: sha(getattr(fresh, n)) for n in opt_buffers(fresh)}
+            restore(tf_path)
+            rec['backbone_loaded'] = dict(loaded_state(fresh), global_step=int(fresh.global_step), untouched=untouched)
     del m, fresh
+    if kind in ('yolov3', 'refinedet') and torch.device(device).type != 'cpu':
+        g, images, gt, lr = build(kind, size, engine, device, use_graph=True)
+        g.set_batch(images, gt)
+        for _ in range(5):
+            loss = float(torch.as_tensor(g.train_step(lr)).reshape(-1)[0].item())
+        rec['graph_steps'] = dict(state(g), loss=loss.hex(), captured=g._graph is not None)
+        del g
     t, images, _, _ = build(kind, size, 'f32', device, mode='test')
     t.load_oracle_params(params)
     try:
