@@ -1,9 +1,12 @@
 """The host plumbing every detector class shares: the flat parameter store, the constructor prologue, batch staging, the step skeleton, the epoch
-loop, torch and tf.train.Saver checkpoints and the data-parallel hook.  No kernel launch order lives here: a class still owns its layer list, `_build`,
-`_forward`, `_loss` and `_backward_iter`.  (ssd300.SSD300 keeps a step of its own: three streams, recorded lists, split graphs.)
+loop, torch and tf.train.Saver checkpoints and the data-parallel hook.  No kernel launch order lives here: a class owns its layer list, `_build`,
+`_forward`, `_loss` and `_backward_iter`; what those have in common between classes -- the layout and initialisation loop, the dgrad-filter table, the two
+backward planners (shared / owned gradient buffers), the pre-activation ResNet + pyramid of RetinaNet and FCOS, the conv + batch-norm op of CenterNet and
+RefineDet320 -- is graph.py.  (ssd300.SSD300 keeps a step of its own: three streams, recorded lists, split graphs.)
 
 What a class provides:
-  * `specs` and the layout: `pinfo` (and `sinfo` if it has moving statistics) name -> (offset, shape) into the flat buffers, then `_alloc_flat`;
+  * `specs` and the layout: `pinfo` (and `sinfo` if it has moving statistics) name -> (offset, shape) into the flat buffers, then `_alloc_flat`
+    (graph.init_parameters from the class's graph.Row list);
   * `_logical_cin(layer)`: the un-padded input-channel count of a layer's filter (`get_param` cuts the pad channels off with it);
   * `_prologue(...)` at the top of its constructor, then `_set_engine(...)` with its own engine default;
   * the step: `_forward(training)`, `_loss(grad_scale)`, `_backward_iter()` and `_step_loss()`, the value train_step returns.  Where it differs from the
@@ -30,7 +33,7 @@ from ._lib import BF16, F32, F32X3
 
 class _Act:
     """rows x pitch activation.  Its gradient: `gid` names the buffer it shares with its residual partners (YOLOv3, RetinaNet, FCOS), or `g` is the
-    buffer itself, allocated by the class's _build_backward (CenterNet, RefineDet320).  `vgg`: a bias + ReLU layer's output (its ReLU mask is the
+    buffer itself, allocated by graph.OwnedGradients.emit (CenterNet, RefineDet320).  `vgg`: a bias + ReLU layer's output (its ReLU mask is the
     activation); alloc=False: a prediction layer whose rows live in the class's prediction tensor"""
 
     def __init__(self, name, N, H, W, C, ld, dtype, dev, vgg=False, alloc=True):

@@ -27,7 +27,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import heads, ops
+from . import graph, heads, ops
 from ._lib import BF16
 from .base import DetectorBase, _Act
 from .warmup import F32Warmup
@@ -73,7 +73,7 @@ def layer_specs(num_classes):
     return specs
 
 
-class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
+class CenterNet(heads.BatchedInference, F32Warmup, graph.OwnedGradients, DetectorBase):
     OPT_BUFFERS = ('M1', 'M2')                                 # Adam's m and v
     OPT_BLOB_KEYS = ('adam_m', 'adam_v')
     OPT_NOT_RESTORED = 'parameter layout differs from this model ({} vs {} entries): Adam moments NOT restored'
@@ -103,34 +103,15 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
         self._warmup_setup(config, data_provider, 'compute_dtype' in config)
 
     # ------------------------------------------------------------------ parameters
-    def _wshape(self, spec):
-        _, kind, cin, cout, k, _, _, _ = spec
-        kout, kin = (cout, cin) if kind == 'conv' else (cin, cout)             # dconv: the filter of the conv it is the gradient of
-        return (kout, k, k, ops.pad_to(kin, self.chunk)), kin
+    @staticmethod
+    def _rows(specs):
+        """dconv: the filter [cin][k][k][cout] of the conv it is the gradient of"""
+        return [graph.Row(name, (cout, k, k, cin) if kind == 'conv' else (cin, k, k, cout), cout, cout, True, cin * k * k)
+                for name, kind, cin, cout, k, _, _, _ in specs]
 
     def _init_parameters(self, seed):
-        pinfo, sinfo = OrderedDict(), OrderedDict()
-        off = soff = 0
-        self._cin = {}
-        for spec in self.specs:
-            name, cout = spec[0], spec[3]
-            wshape, kin = self._wshape(spec)
-            self._cin[name] = kin
-            for suffix, shape in (('.w', wshape), ('.b', (cout,)), ('.gamma', (cout,)), ('.beta', (cout,))):
-                pinfo[name + suffix] = (off, shape)
-                off += ops.pad_to(int(np.prod(shape)), 64)
-            for suffix in ('.mmean', '.mvar'):
-                sinfo[name + suffix] = (soff, (cout,))
-                soff += ops.pad_to(cout, 64)
-        self.pinfo, self.sinfo = pinfo, sinfo
-        self._alloc_flat(off, soff)
+        graph.init_parameters(self, self._rows(self.specs), seed)
         self.Mom = self.M1                                     # (name the data-parallel / checkpoint helpers of the other classes use)
-        g = torch.Generator().manual_seed(seed)
-        for name, kind, cin, cout, k, _, _, _ in self.specs:
-            kout, kin = (cout, cin) if kind == 'conv' else (cin, cout)
-            self.set_param(name + '.w', torch.randn(kout, k, k, kin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-            self.param(name + '.gamma').fill_(1.0)
-            self.stat(name + '.mvar').fill_(1.0)
 
     def _check_oracle_param(self, k, v):
         if k.endswith('.b') and self._layer_kind[k[:-2]] == 'dconv' and float(torch.as_tensor(v).abs().max()) != 0.0:
@@ -154,26 +135,10 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
             return a
 
         def layer(src, out_f32=False):
+            """conv / transposed conv + batch norm (+ ReLU): graph.conv_bn without dilation, mask or prediction tensor"""
             name, kind, cin, cout, k, stride, relu, ghost = next(it)
-            assert not ghost and cin == src.C, (name, cin, src.C)
-            ldz = ops.pad_to(cout, ch)
-            if kind == 'conv':
-                d = ops.conv_desc(N, src.H, src.W, ops.pad_to(cin, ch), src.ld, cout, ldz, k, stride, 1, self.CDT, self.CDT)
-                Ho, Wo = d.Ho, d.Wo
-            else:                                               # the stride-2 conv this layer is the gradient of: [2H,2W,cout] -> [H,W,cin]
-                Ho, Wo = src.H * stride, src.W * stride
-                d = ops.conv_desc(N, Ho, Wo, ldz, ldz, cin, src.ld, k, stride, 1, self.CDT, self.CDT)
-                assert d.Ho == src.H and d.Wo == src.W
-            self.desc[name] = d
-            z = _Act(name + '.z', N, Ho, Wo, cout, ldz, dt, dev)
-            y = act(name, Ho, Wo, cout, out_f32)
-            self.z[name] = z
-            self.bnsave[name] = (torch.zeros(cout, device=dev), torch.zeros(cout, device=dev))
-            self._max_ws = max(self._max_ws, ops.bn_workspace_bytes(z.M, cout))
-            self._max_z = max(self._max_z, z.M * ldz)
-            self._max_scr = max(self._max_scr, src.M * src.ld)
-            self.plan.append(('layer', name, kind, src, z, y, 1 if relu else 0))
-            return y
+            assert not ghost
+            return graph.conv_bn(self, (name, kind, cin, cout, k, stride, 1, relu), src, lambda Ho, Wo: act(name, Ho, Wo, cout, out_f32))
 
         def ghost():
             spec = next(it)
@@ -228,51 +193,34 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
         self.size = self.size_act.t.view(N, self.size_act.H, self.size_act.W, 2)
         self.ws = torch.zeros(self._max_ws, dtype=torch.uint8, device=dev)
         # dgrad-layout filters: the backward of every conv but the first, and the FORWARD of every transposed conv
-        self.wt, entries = {}, []
-        for spec in self.specs:
-            name, kind, cin, cout, k, _, _, ghost_ = spec
-            if ghost_ or name == 'c0':
-                continue
-            (kout, _, _, kin_pad), _ = self._wshape(spec)
-            kp = ops.pad_to(kout, ch)
-            self.wt[name] = torch.zeros(kin_pad * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], kout, k, k, kin_pad, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        graph.filter_table(self, self._rows(s for s in self.specs if not s[7] and s[0] != 'c0'))
         self.loss_ws = ops.centernet_workspace(N, self.kp_act.H, self.kp_act.W, self.num_classes, dev)
         if self.mode == 'train':
             self._build_backward(N, dt, dev)
         self._refresh_operand_copies()
 
     def _build_backward(self, N, dt, dev):
-        self.zg = torch.zeros(self._max_z, dtype=dt, device=dev)             # d(pre-BN conv output): lives inside one layer
-        self.scr = torch.zeros(self._max_scr, dtype=dt, device=dev)          # an input gradient on its way to being accumulated
+        self._alloc_backward()
+        emit, written = self.emit, self._written
         self.d_kp, self.d_off, self.d_size = torch.zeros_like(self.keypoints), torch.zeros_like(self.offset), torch.zeros_like(self.size)
         self.kp_act.g, self.off_act.g, self.size_act.g = (t.view(a.M, a.ld) for t, a in ((self.d_kp, self.kp_act), (self.d_off, self.off_act),
                                                                                         (self.d_size, self.size_act)))
-        written = {id(self.kp_act), id(self.off_act), id(self.size_act)}
-
-        def emit(a):
-            """this consumer's contribution to d(a): first writer -> write, later ones -> accumulate"""
-            acc = id(a) in written
-            written.add(id(a))
-            if a.g is None and a is not self.input:
-                a.g = torch.zeros(a.M, a.ld, dtype=dt, device=dev)
-            return acc
+        written.update((id(self.kp_act), id(self.off_act), id(self.size_act)))
         # Round 6: an input of a sum whose ONLY consumer is that sum has d(input) = d(sum) exactly: it SHARES the sum's gradient buffer instead of receiving a
         # copy of it (DLA's aggregation nodes and residual sums: 85 add2d launches per step were 6.5 % of the step, a good part of them such copies).  Nobody
         # writes into a shared buffer again -- every reader (the producer's batch-norm / pool backward, another sum) only reads d(output).
         consumers = {}
         for op in self.plan:
-            for a in ([op[3]] if op[0] == 'layer' else op[1] if op[0] == 'add' else [op[1]]):
+            for a in ([op[3]] if op[0] == 'bn' else op[1] if op[0] == 'add' else [op[1]]):
                 consumers[id(a)] = consumers.get(id(a), 0) + 1
         self.bplan = []
         self.shared_grads = 0
         for op in reversed(self.plan):
             kind = op[0]
-            if kind == 'layer':
-                _, name, lk, src, z, y, relu = op
-                assert id(y) in written, name
-                self.bplan.append(('layer', name, lk, src, z, y, relu, emit(src) if src is not self.input else False))
+            if kind == 'bn':
+                src, y = op[3], op[5]
+                assert id(y) in written, op[1]
+                self.bplan.append(op + (emit(src) if src is not self.input else False,))
             elif kind == 'add':
                 _, ins, y = op
                 assert id(y) in written
@@ -300,15 +248,8 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
             ops.preprocess(self.images, (0., 0., 0.), self.input.ld, self.DT, self.input.t)
         for op in self.plan:
             kind = op[0]
-            if kind == 'layer':
-                _, name, lk, src, z, y, relu = op
-                if lk == 'conv':
-                    ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), z.t, False)
-                else:                                           # transposed conv = dgrad of its stride-2 conv (bias: exactly 0, see load_oracle_params)
-                    ops.conv2d_dgrad(self.desc[name], src.t, src.ld, self.wt[name], None, z.t, False)
-                sm, si = self.bnsave[name]
-                ops.bn_fwd(z.t, z.M, z.C, z.ld, self.param(name + '.gamma'), self.param(name + '.beta'), self.stat(name + '.mmean'),
-                           self.stat(name + '.mvar'), sm, si, training, relu, y.t, y.ld, z.M, 0, self.ws)
+            if kind == 'bn':
+                graph.conv_bn_fwd(self, op, training)
             elif kind == 'add':
                 _, ins, y = op
                 ops.add2d(ins[0].t, ins[0].ld, ins[1].t, ins[1].ld, y.t, y.ld, y.M, y.ld)
@@ -325,37 +266,15 @@ class CenterNet(heads.BatchedInference, F32Warmup, DetectorBase):
         ops.centernet_loss(self.keypoints, self.offset, self.size, self.gt, STRIDE, grad_scale, self.loss_parts, self.d_kp, self.d_off, self.d_size,
                            self.loss_ws)
 
-    def _into(self, a, acc):
-        """destination of a kernel that can only overwrite: the gradient buffer itself (first writer) or the scratch (then added)"""
-        return self.scr[: a.M * a.ld].view(a.M, a.ld) if acc else a.g
-
-    def _fold(self, a, acc):
-        if acc:
-            ops.add2d(a.g, a.ld, self.scr[: a.M * a.ld].view(a.M, a.ld), a.ld, a.g, a.ld, a.M, a.ld)
-
     def _backward_iter(self):
         for op in self.bplan:
             kind = op[0]
-            if kind == 'layer':
-                _, name, lk, src, z, y, relu, acc = op
-                zg = self.zg[: z.M * z.ld].view(z.M, z.ld)
-                sm, si = self.bnsave[name]
-                ops.bn_bwd(z.t, y.t if relu else None, y.g, z.M, z.C, z.ld, y.ld, z.M, 0, self.param(name + '.gamma'), sm, si, relu, zg,
-                           self._flat(name + '.gamma', self.G), self._flat(name + '.beta', self.G), self.ws)
-                # the bias feeds a batch norm: its gradient is exactly zero (only weight decay acts on it)
-                if lk == 'conv':
-                    ops.conv2d_wgrad(self.desc[name], src.t, zg, z.ld, self._flat(name + '.w', self.G), None)
-                    if src is not self.input:
-                        ops.conv2d_dgrad(self.desc[name], zg, z.ld, self.wt[name], None, src.g, acc)
-                else:
-                    # filter gradient of the underlying conv with the operands swapped: its "input" is d(z), its "output gradient" the layer's input
-                    ops.conv2d_wgrad(self.desc[name], zg, src.t, src.ld, self._flat(name + '.w', self.G), None)
-                    ops.conv2d_fwd(self.desc[name], zg, self._flat(name + '.w', self.Pc), None, self._into(src, acc), False)
-                    self._fold(src, acc)
-                yield name
+            if kind == 'bn':
+                graph.conv_bn_bwd(self, op)
+                yield op[1]
             elif kind == 'add':
                 _, ins, y = op
-                for a, acc in ins:
+                for a, acc in ins:                              # (accumulating: d(a) first, d(y) second -- refinedet.py's binary sum passes them the other way round)
                     if acc:
                         ops.add2d(a.g, a.ld, y.g, y.ld, a.g, a.ld, a.M, a.ld)
                     else:

@@ -20,10 +20,9 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import heads, ops
+from . import graph, heads, ops
 from .base import DetectorBase, _Act
 from .voc_eval import EvaluateMixin
 from .warmup import F32Warmup
@@ -76,7 +75,7 @@ def layer_specs(num_classes):
 HEAD_LAYERS = 11                                               # the last 11 specs: 6 classifier-head + 5 regress-head layers, shared by the levels
 
 
-class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
+class FCOS(EvaluateMixin, F32Warmup, graph.SharedGradients, DetectorBase):
     def __init__(self, config, data_provider):
         self._prologue(config, data_provider)
         self.data_shape = config['data_shape']
@@ -90,24 +89,11 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
         self._warmup_setup(config, data_provider, 'compute_dtype' in config)
 
     # ------------------------------------------------------------------ parameters
-    def param_layout(self):
-        pinfo = OrderedDict()
-        off = 0
-        for name, cin, cout, k, _, gnc, _ in self.specs:
-            for suffix, shape in (('.w', (cout, k, k, ops.pad_to(cin, self.chunk))), ('.b', (cout,)), ('.gamma', (gnc,)), ('.beta', (gnc,))):
-                pinfo[name + suffix] = (off, shape)
-                off += ops.pad_to(int(np.prod(shape)), 64)
-        return pinfo, off
+    def _rows(self, specs):                                     # (group norm: no moving statistics, so no S)
+        return [graph.Row(name, (cout, k, k, cin), cout, gnc, False, cin * k * k, bias_init) for name, cin, cout, k, _, gnc, bias_init in specs]
 
     def _init_parameters(self, seed):
-        self.pinfo, off = self.param_layout()
-        self._alloc_flat(off)
-        self._cin = {s[0]: s[1] for s in self.specs}
-        g = torch.Generator().manual_seed(seed)
-        for name, cin, cout, k, _, _, bias_init in self.specs:
-            self.set_param(name + '.w', torch.randn(cout, k, k, cin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-            self.param(name + '.b').fill_(float(bias_init))
-            self.param(name + '.gamma').fill_(1.0)
+        graph.init_parameters(self, self._rows(self.specs), seed)
 
     # ------------------------------------------------------------------ the graph
     def _build(self):
@@ -119,23 +105,11 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
         self.plan, self.desc, self.gnsave, self.acts = [], {}, {}, {}
         it = iter(self.specs)
         self._max_scr = 0
-        groups = {}
+        self._groups = {}
 
-        def find(g):
-            while groups.setdefault(g, g) != g:
-                g = groups[g]
-            return g
-        self.find = find
-
-        def act(name, H_, W_, C_):
-            a = _Act(name, N, H_, W_, C_, ops.pad_to(C_, ch), dt, dev)
-            self.acts[name] = a
-            return a
-
-        def conv_desc(name, src, cout, k, stride, ldy):
-            d = ops.conv_desc(N, src.H, src.W, src.ld, src.ld, cout, ldy, k, stride, 1, self.CDT, self.CDT)
-            self.desc[name] = d
-            return d
+        def gnsave(name, a, gnc=None):
+            self.gnsave[name] = torch.zeros(N, GROUPS, 2, device=dev)
+            self._max_scr = max(self._max_scr, a.M * a.ld)
 
         def gnconv(x, spec=None, level=None):
             """group norm -> ReLU -> conv(bias): returns the conv output.  `spec`, `level`: a shared head layer applied at one
@@ -143,53 +117,16 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
             pname, cin, cout, k, stride, gnc, _ = next(it) if spec is None else spec
             name = pname if level is None else f'{pname}@{level}'
             assert cin == x.C == gnc and gnc % GROUPS == 0, (name, cin, x.C)
-            y = act(name + '.y', x.H, x.W, x.C)
-            d = conv_desc(name, y, cout, k, stride, ops.pad_to(cout, ch))
-            out = act(name, d.Ho, d.Wo, cout)
-            self.gnsave[name] = torch.zeros(N, GROUPS, 2, device=dev)
-            self._max_scr = max(self._max_scr, y.M * y.ld)
+            y = graph.new_act(self, name + '.y', x.H, x.W, x.C)
+            d = graph.conv_desc(self, name, y, cout, k, stride, ops.pad_to(cout, ch))
+            out = graph.new_act(self, name, d.Ho, d.Wo, cout)
+            gnsave(name, y)
             self.plan.append(('gnconv', name, x, y, out, pname))
             return out
 
-        def add(a, b):
-            y = act(f'sum{len(self.plan)}', a.H, a.W, a.C)
-            groups[find(a.gid)] = find(y.gid)
-            groups[find(b.gid)] = find(y.gid)
-            self.plan.append(('add', a, b, y))
-            return y
-
-        def resize_add(lat, top):
-            y = act(f'total{len(self.plan)}', lat.H, lat.W, lat.C)
-            groups[find(lat.gid)] = find(y.gid)
-            self.plan.append(('resize_add', lat, top, y))
-            return y
-
-        name, cin, cout, k, stride, gnc, _ = next(it)
-        d = conv_desc(name, self.input, cout, k, stride, ops.pad_to(cout, ch))
-        z = act(name + '.z', d.Ho, d.Wo, cout)
-        y = act(name, d.Ho, d.Wo, cout)
-        self.gnsave[name] = torch.zeros(N, GROUPS, 2, device=dev)
-        self._max_scr = max(self._max_scr, z.M * z.ld)
-        self.plan.append(('stem', name, self.input, z, y))
-        Hp, pt, _ = ops.same_pad(y.H, 3, 2)
-        Wp, pl, _ = ops.same_pad(y.W, 3, 2)
-        x = act('pool1', Hp, Wp, cout)
-        self.plan.append(('pool', y, x, 3, 2, pt, pl))
-        feats = []
-        for blocks in BLOCKS:
-            for _ in range(blocks):
-                branch = gnconv(gnconv(gnconv(x)))
-                x = add(branch, gnconv(x))
-            feats.append(x)
+        feats = graph.preact_resnet(self, it, BLOCKS, gnconv, gnsave)
         c3, c4, c5 = gnconv(feats[-3]), gnconv(feats[-2]), gnconv(feats[-1])
-        p5 = gnconv(c5)
-        total4 = resize_add(gnconv(c4), p5)
-        p4 = gnconv(total4)
-        total3 = resize_add(gnconv(c3), total4)
-        p3 = gnconv(total3)
-        p6 = gnconv(p5)
-        p7 = gnconv(p6)
-        self.levels = [p3, p4, p5, p6, p7]
+        self.levels = graph.fpn(self, gnconv, c3, c4, c5)
         self.conf = [torch.zeros(N, a.H, a.W, self.num_classes, device=dev) for a in self.levels]
         self.reg = [torch.zeros(N, a.H, a.W, 4, device=dev) for a in self.levels]
         self.center = [torch.zeros(N, a.H, a.W, 1, device=dev) for a in self.levels]
@@ -205,66 +142,37 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
             for j in range(4):
                 r = gnconv(r, head[6 + j], l)
             self.plan.append(('pred', gnconv(r, head[10], l), self.reg, l, True))       # tf.exp on the distances (FCOS.py:363)
-        self.wt, entries = {}, []
-        for name, cin, cout, k, _, _, _ in self.specs[1:]:
-            kp, cpad = ops.pad_to(cout, ch), ops.pad_to(cin, ch)        # dgrad-layout filter: one per PARAMETER (shared by the levels)
-            self.wt[name] = torch.zeros(cpad * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], cout, k, k, cpad, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        graph.filter_table(self, self._rows(self.specs[1:]))            # dgrad-layout filters: one per PARAMETER (shared by the levels)
         if self.mode == 'train':
             self._build_backward(N, dt, dev)
         self._refresh_operand_copies()
 
     def _build_backward(self, N, dt, dev):
-        find = self.find
         self.dconf = [torch.zeros_like(t) for t in self.conf]
         self.dreg = [torch.zeros_like(t) for t in self.reg]
         self.dcenter = [torch.zeros_like(t) for t in self.center]
         self.scr_y = torch.zeros(self._max_scr, dtype=dt, device=dev)          # d(relu(gn(x))): lives inside one layer
         self.gn_ws = ops.gn_workspace(N, max(s[5] for s in self.specs), dev)
-        written = set()
+        io = dict(graph.TRUNK_IO, pred=lambda op: ([], [op[1]]), gnconv=lambda op: ([op[4]], [op[2]]))
         seen_params = set()
-        self.bplan = []
-        for op in reversed(self.plan):
+        self.g, self.bplan = {}, []
+        for op, acc in self._reverse(io):
             kind = op[0]
-            if kind == 'pred':
-                self.bplan.append(op)
-                written.add(find(op[1].gid))
-            elif kind == 'gnconv':
+            if kind == 'gnconv':
                 _, name, x, y, out, pname = op
-                assert find(out.gid) in written, name
                 # a shared head layer: its norm's d(gamma), d(beta) accumulate over the levels (the filter / bias gradients always
                 # accumulate); the layer is final -- for the gradient all-reduce -- after the LAST level processed (level 0)
                 first_use = pname not in seen_params
                 seen_params.add(pname)
                 last_use = name == pname or name.endswith('@0')
-                self.bplan.append(('gnconv', name, x, y, out, find(x.gid) in written, pname, not first_use, last_use))
-                written.add(find(x.gid))
-            elif kind == 'add':
-                assert find(op[3].gid) in written
+                self.bplan.append(('gnconv', name, x, y, out, acc, pname, not first_use, last_use))
             elif kind == 'resize_add':
-                _, lat, top, y = op
-                assert find(y.gid) in written
-                self.bplan.append(('resize_add', lat, top, y, find(top.gid) in written))
-                written.add(find(top.gid))
-            elif kind == 'pool':
-                _, x, y, k, s, pt, pl = op
-                assert find(y.gid) in written
+                self.bplan.append(op + (acc,))
+            elif kind != 'add':
                 self.bplan.append(op)
-                written.add(find(x.gid))
-            else:
-                self.bplan.append(op)
-        self.g = {}
-        for a in self.acts.values():
-            gid = find(a.gid)
-            if gid in written and gid not in self.g:
-                self.g[gid] = torch.zeros(a.M, a.ld, dtype=dt, device=dev)
         self.loss_img = torch.zeros(N, device=dev)
         self.loss_ws = ops.fcos_workspace(self.conf, N, dev)
         self.gt = None
-
-    def grad_of(self, a):
-        return self.g[self.find(a.gid)]
 
     # ------------------------------------------------------------------ forward / loss / backward
     def _gn_relu(self, name, x, y, pname=None):
@@ -279,26 +187,16 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
                 _, name, x, y, out, pname = op
                 self._gn_relu(name, x, y, pname)
                 ops.conv2d_fwd(self.desc[name], y.t, self._flat(pname + '.w', self.Pc), self.param(pname + '.b'), out.t, False)
-            elif kind == 'add':
-                _, a, b, y = op
-                ops.add2d(a.t, a.ld, b.t, b.ld, y.t, y.ld, y.M, y.ld)
-            elif kind == 'resize_add':
-                _, lat, top, y = op
-                ops.add2d(lat.t, lat.ld, None, 0, y.t, y.ld, y.M, y.ld)
-                ops.resize_bilinear_fwd(top.t, top.ld, y.t, y.ld, top.N, top.H, top.W, y.H, y.W, top.C, True)
             elif kind == 'pred':
                 _, c, targets, l, is_exp = op
                 if is_exp:
                     ops.exp_rows_to_f32(c.t, c.ld, targets[l], c.M, c.C)
                 else:
                     ops.rows_to_f32(c.t, c.ld, targets[l], c.C, c.M, 0, c.M, c.C)
-            elif kind == 'stem':
-                _, name, src, z, y = op
-                ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), z.t, False)
-                self._gn_relu(name, z, y)
-            else:
-                _, x, y, k, s, pt, pl = op
-                ops.maxpool_fwd(x.t, y.t, x.N, x.H, x.W, x.C, x.ld, y.H, y.W, k, s, pt, pl)
+            else:                                               # add, resize_add, pool, the stem's convolution
+                graph.trunk_fwd(self, op)
+                if kind == 'stem':
+                    self._gn_relu(op[1], op[3], op[4])
 
     def _loss(self, grad_scale):
         ops.fcos_loss(self.conf, self.reg, self.center, self.gt, grad_scale, self.loss_img, self.dconf, self.dreg, self.dcenter, self.loss_ws)
@@ -324,12 +222,8 @@ class FCOS(EvaluateMixin, F32Warmup, DetectorBase):
                            self._flat(pname + '.beta', self.G), self.gn_ws)
                 if last_use:
                     yield pname
-            elif kind == 'resize_add':
-                _, lat, top, y, acc = op
-                ops.resize_bilinear_bwd(self.grad_of(y), y.ld, self.grad_of(top), top.ld, top.N, top.H, top.W, y.H, y.W, top.C, acc)
-            elif kind == 'pool':
-                _, x, y, k, s, pt, pl = op
-                ops.maxpool_bwd(x.t, y.t, self.grad_of(y), self.grad_of(x), x.N, x.H, x.W, x.C, x.ld, y.H, y.W, k, s, pt, pl)
+            elif kind in ('resize_add', 'pool'):
+                graph.trunk_bwd(self, op)
             else:                                               # stem: conv -> GN -> ReLU (its bias DOES have a gradient: group norm is not
                 _, name, src, z, y = op                        # invariant to a per-channel shift inside a group)
                 dzs = self.scr_y[: z.M * z.ld].view(z.M, z.ld)

@@ -18,14 +18,12 @@ ssd300.py: the gradient buffer of a bias + ReLU activation holds d(pre-activatio
 """
 from __future__ import annotations
 
-import math
 import os
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import heads, ops
+from . import graph, heads, ops
 from .base import DetectorBase, _Act
 from .warmup import F32Warmup
 
@@ -67,7 +65,7 @@ def layer_specs(num_classes):
     return s
 
 
-class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
+class RefineDet320(heads.BatchedInference, F32Warmup, graph.OwnedGradients, DetectorBase):
     # RefineDet320 / PFPNetR do not pass the bf16 gate (one head layer loses its direction); YOLOv2 does.  Round 4: their default is the f32 engine with
     # ODTK_F32X3 convolution descriptors (three bf16 MFMA products per f32 product): it passes the same gate at RANDOM INITIALISATION (minimum cosine 0.998 / 0.999
     # against the exact f32 engine) at 2.1x the exact engine's throughput (607 / 598 against 282 / 286 images/s)
@@ -99,47 +97,24 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
         self._load_pretraining_weight()
 
     # ------------------------------------------------------------------ parameters
-    def _wshape(self, spec):
-        _, kind, cin, cout, k, _, _, _ = spec
-        kout, kin = (cout, cin) if kind != 'dconv' else (cin, cout)
-        return (kout, k, k, ops.pad_to(kin, self.chunk)), kin
-
     def _extra_layer_params(self, spec):
         return ()
 
-    def _init_parameters(self, seed):
-        pinfo, sinfo = OrderedDict(), OrderedDict()
-        off = soff = 0
-        self._cin, self._kind = {}, {}
+    def _rows(self, specs):
+        """'vgg': bias + ReLU, no norm; 'dconv': the filter [cin][k][k][cout] of the conv it is the gradient of.  In front of a layer: its
+        _extra_layer_params (the depthwise filter of a separable layer, lhrcnn.LHRCNN); behind L2_AFTER: the two L2-norm scalars"""
+        rows = []
+        for spec in specs:
+            name, kind, cin, cout, k = spec[:5]
+            after = (('feat1_l2_norm', (1,)), ('feat2_l2_norm', (1,))) if name == self.L2_AFTER else ()
+            rows.append(graph.Row(name, (cout, k, k, cin) if kind != 'dconv' else (cin, k, k, cout), cout, None if kind == 'vgg' else cout, True,
+                                  cin * k * k, 0., self._extra_layer_params(spec), after))
+        return rows
 
-        def add(name, shape):
-            nonlocal off
-            pinfo[name] = (off, tuple(shape))
-            off += ops.pad_to(int(np.prod(shape)), 64)
-        for i, spec in enumerate(self.specs):
-            name, kind, cout = spec[0], spec[1], spec[3]
-            wshape, kin = self._wshape(spec)
-            self._cin[name], self._kind[name] = kin, kind
-            for extra, shape in self._extra_layer_params(spec):       # e.g. the depthwise filter of a separable layer (lhrcnn.LHRCNN), created first
-                add(extra, shape)
-            add(name + '.w', wshape); add(name + '.b', (cout,))
-            if kind != 'vgg':
-                add(name + '.gamma', (cout,)); add(name + '.beta', (cout,))
-                for suffix in ('.mmean', '.mvar'):
-                    sinfo[name + suffix] = (soff, (cout,))
-                    soff += ops.pad_to(cout, 64)
-            if name == self.L2_AFTER:
-                add('feat1_l2_norm', (1,)); add('feat2_l2_norm', (1,))
-        self.pinfo, self.sinfo = pinfo, sinfo
-        self._alloc_flat(off, soff)
-        g = torch.Generator().manual_seed(seed)
-        for name, kind, cin, cout, k, _, _, _ in self.specs:
-            kout, kin = (cout, cin) if kind != 'dconv' else (cin, cout)
-            self.set_param(name + '.w', torch.randn(kout, k, k, kin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-            if kind != 'vgg':
-                self.param(name + '.gamma').fill_(1.0)
-                self.stat(name + '.mvar').fill_(1.0)
-        if 'feat1_l2_norm' in pinfo:
+    def _init_parameters(self, seed):
+        self._kind = {s[0]: s[1] for s in self.specs}
+        graph.init_parameters(self, self._rows(self.specs), seed)
+        if 'feat1_l2_norm' in self.pinfo:
             self.param('feat1_l2_norm').fill_(10.0)
             self.param('feat2_l2_norm').fill_(8.0)
 
@@ -197,30 +172,14 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
 
         def bn(name, src, out=None):
             """conv / transposed conv + batch norm (+ ReLU); out = (tensor, first row, width): the output goes straight into a prediction tensor"""
-            _, kind, cin, cout, k, stride, dil, relu = spec[name]
-            assert cin == src.C, (name, cin, src.C)
-            ldz = ops.pad_to(cout, ch)
-            if kind == 'conv':
-                d = ops.conv_desc(N, src.H, src.W, ops.pad_to(cin, ch), src.ld, cout, ldz, k, stride, dil, self.CDT, self.CDT)
-                Ho, Wo = d.Ho, d.Wo
-            else:
-                Ho, Wo = src.H * stride, src.W * stride
-                d = ops.conv_desc(N, Ho, Wo, ldz, ldz, cin, src.ld, k, stride, 1, self.CDT, self.CDT)
-                assert d.Ho == src.H and d.Wo == src.W
-            self.desc[name] = d
-            z = _Act(name + '.z', N, Ho, Wo, cout, ldz, dt, dev)
-            self.z[name] = z
-            if out is None:
-                y = act(name, Ho, Wo, cout)
-            else:
-                y = _Act(name, N, Ho, Wo, cout, cout, torch.float32, dev, alloc=False)
-                self.acts[name] = y
-            self.bnsave[name] = (torch.zeros(cout, device=dev), torch.zeros(cout, device=dev))
-            self._max_ws = max(self._max_ws, ops.bn_workspace_bytes(z.M, cout))
-            self._max_z = max(self._max_z, z.M * ldz)
-            self._max_scr = max(self._max_scr, src.M * src.ld)
-            self.plan.append(('bn', name, kind, src, z, y, int(relu), out))          # 0 none | 1 ReLU | 2 leaky_relu(0.1)
-            return y
+            cout = spec[name][3]
+
+            def new_y(Ho, Wo):
+                if out is None:
+                    return act(name, Ho, Wo, cout)
+                self.acts[name] = _Act(name, N, Ho, Wo, cout, cout, torch.float32, dev, alloc=False)
+                return self.acts[name]
+            return graph.conv_bn(self, spec[name], src, new_y, out)
 
         def pool(name, x, k, s):
             Ho, pt, _ = ops.same_pad(x.H, k, s)
@@ -274,16 +233,7 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
         from types import SimpleNamespace
         self._build_model(SimpleNamespace(vgg=vgg, bn=bn, pool=pool, l2norm=l2norm, resize=resize, avgpool=avgpool, add=add, concat=concat, act=act, dw=dw, sink=sink))
         self.ws = torch.zeros(self._max_ws, dtype=torch.uint8, device=dev)
-        self.wt, entries = {}, []
-        for sp in self.specs:
-            name, kind, cin, cout, k = sp[0], sp[1], sp[2], sp[3], sp[4]
-            if name == self.specs[0][0]:                        # the first layer: the input needs no gradient
-                continue
-            (kout, _, _, kin_pad), _ = self._wshape(sp)
-            kp = ops.pad_to(kout, ch)
-            self.wt[name] = torch.zeros(kin_pad * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], kout, k, k, kin_pad, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        graph.filter_table(self, self._rows(self.specs[1:]))         # (not the first layer's: the input needs no gradient)
         if self.mode == 'train':
             self._build_backward(N, dt, dev)
         self._refresh_operand_copies()
@@ -349,16 +299,8 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
 
     def _build_backward(self, N, dt, dev):
         self.loss = None                                        # heads.RefineDetLoss, built with the first batch (needs the ground-truth pad length)
-        self.zg = torch.zeros(self._max_z, dtype=dt, device=dev)
-        self.scr = torch.zeros(self._max_scr, dtype=dt, device=dev)
-        written = set()
-
-        def emit(a):
-            acc = id(a) in written
-            written.add(id(a))
-            if a.g is None and a is not self.input:
-                a.g = torch.zeros(a.M, a.ld, dtype=dt, device=dev)
-            return acc
+        self._alloc_backward()
+        emit, written = self.emit, self._written
         self.bplan = []
         for op in reversed(self.plan):
             kind = op[0]
@@ -419,19 +361,7 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
                 _, name, src, y = op
                 ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), y.t, True)
             elif kind == 'bn':
-                _, name, lk, src, z, y, relu, out = op
-                if lk == 'conv':
-                    ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), z.t, False)
-                else:
-                    ops.conv2d_dgrad(self.desc[name], src.t, src.ld, self.wt[name], None, z.t, False)
-                sm, si = self.bnsave[name]
-                if out is None:
-                    dst, ldy, rpi, stride = y.t, y.ld, z.M, 0
-                else:
-                    dst, _, stride = self._pred_view(out)
-                    ldy, rpi = z.C, z.H * z.W                   # a cell's NA * width outputs are contiguous rows of the prediction tensor
-                ops.bn_fwd(z.t, z.M, z.C, z.ld, self.param(name + '.gamma'), self.param(name + '.beta'), self.stat(name + '.mmean'),
-                           self.stat(name + '.mvar'), sm, si, training, relu, dst, ldy, rpi, stride, self.ws)
+                graph.conv_bn_fwd(self, op, training)
             elif kind == 'pool':
                 _, x, y, k, s, pt = op
                 ops.maxpool_fwd(x.t, y.t, x.N, x.H, x.W, x.C, x.ld, y.H, y.W, k, s, pt, pt)
@@ -457,37 +387,12 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
                 _, a, b, y = op
                 ops.add_relu_fwd(a.t, a.ld, b.t, b.ld, y.t, y.ld, y.M, y.ld)
 
-    def _into(self, a, acc):
-        return self.scr[: a.M * a.ld].view(a.M, a.ld) if acc else a.g
-
-    def _fold(self, a, acc):
-        if acc:
-            ops.add2d(a.g, a.ld, self.scr[: a.M * a.ld].view(a.M, a.ld), a.ld, a.g, a.ld, a.M, a.ld)
-
     def _backward_iter(self):
         for op in self.bplan:
             kind = op[0]
             if kind == 'bn':
-                _, name, lk, src, z, y, relu, out, acc = op
-                zg = self.zg[: z.M * z.ld].view(z.M, z.ld)
-                sm, si = self.bnsave[name]
-                if out is None:
-                    dy, ldy, rpi, stride, yt = y.g, y.ld, z.M, 0, (y.t if relu else None)
-                else:
-                    dy, _, stride = self._pred_view(out, grad=True)
-                    ldy, rpi, yt = z.C, z.H * z.W, None
-                ops.bn_bwd(z.t, yt, dy, z.M, z.C, z.ld, ldy, rpi, stride, self.param(name + '.gamma'), sm, si, relu, zg,
-                           self._flat(name + '.gamma', self.G), self._flat(name + '.beta', self.G), self.ws)
-                mask = src.t if src.vgg else None
-                if lk == 'conv':
-                    ops.conv2d_wgrad(self.desc[name], src.t, zg, z.ld, self._flat(name + '.w', self.G), None)
-                    if src is not self.input:
-                        ops.conv2d_dgrad(self.desc[name], zg, z.ld, self.wt[name], mask, src.g, acc)
-                else:
-                    ops.conv2d_wgrad(self.desc[name], zg, src.t, src.ld, self._flat(name + '.w', self.G), None)
-                    ops.conv2d_fwd(self.desc[name], zg, self._flat(name + '.w', self.Pc), None, self._into(src, acc), False)
-                    self._fold(src, acc)
-                yield name
+                graph.conv_bn_bwd(self, op)
+                yield op[1]
             elif kind == 'vgg':
                 _, name, src, y, acc = op
                 ops.conv2d_wgrad(self.desc[name], src.t, y.g, y.ld, self._flat(name + '.w', self.G), self._flat(name + '.b', self.G))
@@ -511,7 +416,7 @@ class RefineDet320(heads.BatchedInference, F32Warmup, DetectorBase):
                 self._fold(x, acc)
             elif kind == 'add':
                 _, (a, acc_a), (b, acc_b), y = op
-                for t, acc in ((a, acc_a), (b, acc_b)):
+                for t, acc in ((a, acc_a), (b, acc_b)):         # (accumulating: d(y) first, d(t) second -- centernet.py's n-ary sum passes them the other way round)
                     ops.add2d(y.g, y.ld, t.g if acc else None, t.ld, t.g, t.ld, y.M, y.ld)
             elif kind == 'concat':
                 _, srcs, y = op

@@ -29,7 +29,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import heads, ops
+from . import graph, heads, ops
 from .base import DetectorBase, _Act
 
 MEAN_RGB = (123.68, 116.779, 103.979)
@@ -81,7 +81,7 @@ def level_priors(size):
     return out
 
 
-class RetinaNet(heads.BatchedInference, DetectorBase):
+class RetinaNet(heads.BatchedInference, graph.SharedGradients, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         self.is_pretraining = bool(config.get('is_pretraining'))
@@ -114,28 +114,11 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
             self.test_one_image = self._test_one_pretraining_image
 
     # ------------------------------------------------------------------ parameters
-    def param_layout(self):
-        pinfo, sinfo = OrderedDict(), OrderedDict()
-        off = soff = 0
-        for name, cin, cout, k, _, bnc, _ in self.specs:
-            for suffix, shape in (('.w', (cout, k, k, ops.pad_to(cin, self.chunk))), ('.b', (cout,)), ('.gamma', (bnc,)), ('.beta', (bnc,))):
-                pinfo[name + suffix] = (off, shape)
-                off += ops.pad_to(int(np.prod(shape)), 64)
-            for suffix in ('.mmean', '.mvar'):
-                sinfo[name + suffix] = (soff, (bnc,))
-                soff += ops.pad_to(bnc, 64)
-        return pinfo, off, sinfo, soff
+    def _rows(self, specs):
+        return [graph.Row(name, (cout, k, k, cin), cout, bnc, True, cin * k * k, bias_init) for name, cin, cout, k, _, bnc, bias_init in specs]
 
     def _init_parameters(self, seed):
-        self.pinfo, off, self.sinfo, soff = self.param_layout()
-        self._alloc_flat(off, soff)
-        self._cin = {s[0]: s[1] for s in self.specs}
-        g = torch.Generator().manual_seed(seed)
-        for name, cin, cout, k, _, _, bias_init in self.specs:
-            self.set_param(name + '.w', torch.randn(cout, k, k, cin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-            self.param(name + '.b').fill_(float(bias_init))
-            self.param(name + '.gamma').fill_(1.0)
-            self.stat(name + '.mvar').fill_(1.0)
+        graph.init_parameters(self, self._rows(self.specs), seed)
 
     # ------------------------------------------------------------------ the graph
     def _build(self):
@@ -147,82 +130,33 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         self.plan, self.desc, self.bnsave, self.acts = [], {}, {}, {}
         it = iter(self.specs)
         self._max_ws = self._max_scr = 0
-        groups = {}
-
-        def find(g):
-            while groups.setdefault(g, g) != g:
-                g = groups[g]
-            return g
-        self.find = find
-
-        def act(name, H_, W_, C_):
-            a = _Act(name, N, H_, W_, C_, ops.pad_to(C_, ch), dt, dev)
-            self.acts[name] = a
-            return a
+        self._groups = {}
 
         def note(a):
             self._max_ws = max(self._max_ws, ops.bn_workspace_bytes(a.M, a.C))
             self._max_scr = max(self._max_scr, a.M * a.ld)
 
-        def conv_desc(name, src, cout, k, stride, ldy):
-            d = ops.conv_desc(N, src.H, src.W, src.ld, src.ld, cout, ldy, k, stride, 1, self.CDT, self.CDT)
-            self.desc[name] = d
-            return d
+        def bnsave(name, a, bnc):
+            self.bnsave[name] = (torch.zeros(bnc, device=dev), torch.zeros(bnc, device=dev))
+            note(a)
 
         def bnconv(x):
             """batch norm -> ReLU -> conv(bias): returns the conv output"""
             name, cin, cout, k, stride, bnc, _ = next(it)
             assert cin == x.C == bnc, (name, cin, x.C)
-            y = act(name + '.y', x.H, x.W, x.C)                  # relu(bn(x)): the conv's operand
-            d = conv_desc(name, y, cout, k, stride, ops.pad_to(cout, ch))
-            out = act(name, d.Ho, d.Wo, cout)
-            self.bnsave[name] = (torch.zeros(bnc, device=dev), torch.zeros(bnc, device=dev))
-            note(x); note(out)
+            y = graph.new_act(self, name + '.y', x.H, x.W, x.C)                  # relu(bn(x)): the conv's operand
+            d = graph.conv_desc(self, name, y, cout, k, stride, ops.pad_to(cout, ch))
+            out = graph.new_act(self, name, d.Ho, d.Wo, cout)
+            bnsave(name, x, bnc)
+            note(out)
             self.plan.append(('bnconv', name, x, y, out))
             return out
 
-        def add(a, b):
-            y = act(f'sum{len(self.plan)}', a.H, a.W, a.C)
-            groups[find(a.gid)] = find(y.gid)                      # both operands are conv outputs with this single consumer
-            groups[find(b.gid)] = find(y.gid)
-            self.plan.append(('add', a, b, y))
-            return y
-
-        def resize_add(lat, top):
-            y = act(f'total{len(self.plan)}', lat.H, lat.W, lat.C)
-            groups[find(lat.gid)] = find(y.gid)
-            self.plan.append(('resize_add', lat, top, y))
-            return y
-
-        # stem: conv -> batch norm -> ReLU -> 3x3 / stride-2 max pool (RetinaNet.py:260-271)
-        name, cin, cout, k, stride, bnc, _ = next(it)
-        d = conv_desc(name, self.input, cout, k, stride, ops.pad_to(cout, ch))
-        z = act(name + '.z', d.Ho, d.Wo, cout)
-        y = act(name, d.Ho, d.Wo, cout)
-        self.bnsave[name] = (torch.zeros(bnc, device=dev), torch.zeros(bnc, device=dev))
-        note(z)
-        self.plan.append(('stem', name, self.input, z, y))
-        Hp, pt, _ = ops.same_pad(y.H, 3, 2)
-        Wp, pl, _ = ops.same_pad(y.W, 3, 2)
-        x = act('pool1', Hp, Wp, cout)
-        self.plan.append(('pool', y, x, 3, 2, pt, pl))
-        feats = []
-        for i, blocks in enumerate(self.block_list):
-            for _ in range(blocks):
-                branch = bnconv(bnconv(bnconv(x)))
-                x = add(branch, bnconv(x))
-            feats.append(x)
+        # stem: conv -> batch norm -> ReLU -> 3x3 / stride-2 max pool, then the units (RetinaNet.py:260-285)
+        feats = graph.preact_resnet(self, it, self.block_list, bnconv, bnsave)
         if self.is_pretraining:
-            return self._build_pretraining(x, it)
-        f1, f2, f3 = feats[-3:]
-        p5 = bnconv(f3)
-        total4 = resize_add(bnconv(f2), p5)
-        p4 = bnconv(total4)
-        total3 = resize_add(bnconv(f1), total4)
-        p3 = bnconv(total3)
-        p6 = bnconv(p5)
-        p7 = bnconv(p6)
-        self.levels = [p3, p4, p5, p6, p7]
+            return self._build_pretraining(feats[-1], it)
+        self.levels = graph.fpn(self, bnconv, *feats[-3:])
         self.shapes = [(a.H, a.W) for a in self.levels]
         A = sum(h * w * self.num_anchors for h, w in self.shapes)
         self.num_anchor_boxes = A
@@ -238,14 +172,7 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
             off += lvl.H * lvl.W * self.num_anchors
         assert next(it, None) is None and off == A
         self.ws = torch.zeros(self._max_ws, dtype=torch.uint8, device=dev)
-        # dgrad-layout filters (every conv but the stem)
-        self.wt, entries = {}, []
-        for name, cin, cout, k, _, _, _ in self.specs[1:]:
-            d = self.desc[name]
-            kp = self.acts[name].ld
-            self.wt[name] = torch.zeros(d.C * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], cout, k, k, d.C, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        graph.filter_table(self, self._rows(self.specs[1:]))                     # dgrad-layout filters (every conv but the stem)
         # anchors (RetinaNet.py:328-355; x uses the H rate: data_shape[1] is read as the height, :330)
         flat = [v for s in ANCHOR_SIZES for hw in level_priors(s) for v in hw]
         self.anc = ops.retina_anchors(self.data_shape[1], self.shapes, [self.num_anchors] * 5, flat, dev)     # y1x1, y2x2, yx, hw
@@ -254,45 +181,14 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         self._refresh_operand_copies()
 
     def _build_backward(self, N, A, dt, dev):
-        find = self.find
         self.dconf, self.dbox = torch.zeros_like(self.pconf), torch.zeros_like(self.pbox)
         self.scr_y = torch.zeros(self._max_scr, dtype=dt, device=dev)          # d(relu(bn(x))): lives inside one layer
         self.scr_x = torch.zeros(self._max_scr, dtype=dt, device=dev)          # dx of a batch norm whose input already holds a gradient
-        written = set()
-        self.bplan = []
-        for op in reversed(self.plan):
-            kind = op[0]
-            if kind == 'pred':
-                _, c, target, off, width = op
-                self.bplan.append(op)
-                written.add(find(c.gid))
-            elif kind == 'gap':                         # the pre-training head is the gradient source: dx lands in the last sum's buffer
-                self.bplan.append(op)
-                written.add(find(op[1].gid))
-            elif kind == 'bnconv':
-                _, name, x, y, out = op
-                assert find(out.gid) in written, name
-                self.bplan.append(('bnconv', name, x, y, out, find(x.gid) in written))
-                written.add(find(x.gid))
-            elif kind == 'add':
-                assert find(op[3].gid) in written
-            elif kind == 'resize_add':
-                _, lat, top, y = op
-                assert find(y.gid) in written
-                self.bplan.append(('resize_add', lat, top, y, find(top.gid) in written))
-                written.add(find(top.gid))
-            elif kind == 'pool':
-                _, x, y, k, s, pt, pl = op
-                assert find(y.gid) in written
-                self.bplan.append(op)
-                written.add(find(x.gid))
-            else:
-                self.bplan.append(op)
+        # the gradient sources write: a 'pred' into its subnet's last layer, the pre-training head ('gap') into the last sum's buffer
+        source = lambda op: ([], [op[1]])
+        io = dict(graph.TRUNK_IO, pred=source, gap=source, bnconv=lambda op: ([op[4]], [op[2]]))
         self.g = {}
-        for a in self.acts.values():
-            gid = find(a.gid)
-            if gid in written and gid not in self.g:
-                self.g[gid] = torch.zeros(a.M, a.ld, dtype=dt, device=dev)
+        self.bplan = [op + (acc,) if op[0] in ('bnconv', 'resize_add') else op for op, acc in self._reverse(io) if op[0] != 'add']
         P = 1
         i32 = dict(dtype=torch.int32, device=dev)
         self.m_ngt = torch.zeros(N, **i32)
@@ -303,9 +199,6 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         self.m_ws = None
         self.loss_parts = torch.zeros(N, 2, device=dev)
         self.gt = None
-
-    def grad_of(self, a):
-        return self.g[self.find(a.gid)]
 
     # ------------------------------------------------------------------ forward / loss / backward
     def _bn_relu(self, name, x, y, training):
@@ -328,26 +221,16 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
                 _, name, x, y, out = op
                 self._bn_relu(name, x, y, training)
                 ops.conv2d_fwd(self.desc[name], y.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), out.t, False)
-            elif kind == 'add':
-                _, a, b, y = op
-                ops.add2d(a.t, a.ld, b.t, b.ld, y.t, y.ld, y.M, y.ld)
-            elif kind == 'resize_add':
-                _, lat, top, y = op
-                ops.add2d(lat.t, lat.ld, None, 0, y.t, y.ld, y.M, y.ld)
-                ops.resize_bilinear_fwd(top.t, top.ld, y.t, y.ld, top.N, top.H, top.W, y.H, y.W, top.C, True)
             elif kind == 'pred':
                 _, c, target, off, width = op
                 K = self.num_anchors * width
                 ops.rows_to_f32(c.t, c.ld, target[0, off:], K, c.H * c.W, target.shape[1] * width, c.M, K)
             elif kind == 'gap':
                 self._gap_head(training)
-            elif kind == 'stem':
-                _, name, src, z, y = op
-                ops.conv2d_fwd(self.desc[name], src.t, self._flat(name + '.w', self.Pc), self.param(name + '.b'), z.t, False)
-                self._bn_relu(name, z, y, training)
-            else:
-                _, x, y, k, s, pt, pl = op
-                ops.maxpool_fwd(x.t, y.t, x.N, x.H, x.W, x.C, x.ld, y.H, y.W, k, s, pt, pl)
+            else:                                               # add, resize_add, pool, the stem's convolution
+                graph.trunk_fwd(self, op)
+                if kind == 'stem':
+                    self._bn_relu(op[1], op[3], op[4], training)
 
     def _loss(self, grad_scale):
         N, P = self.gt.shape[0], self.gt.shape[1]
@@ -384,12 +267,8 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
                     gx = self.grad_of(x)
                     ops.add2d(gx, x.ld, dx, x.ld, gx, x.ld, x.M, x.ld)
                 yield name
-            elif kind == 'resize_add':
-                _, lat, top, y, acc = op
-                ops.resize_bilinear_bwd(self.grad_of(y), y.ld, self.grad_of(top), top.ld, top.N, top.H, top.W, y.H, y.W, top.C, acc)
-            elif kind == 'pool':
-                _, x, y, k, s, pt, pl = op
-                ops.maxpool_bwd(x.t, y.t, self.grad_of(y), self.grad_of(x), x.N, x.H, x.W, x.C, x.ld, y.H, y.W, k, s, pt, pl)
+            elif kind in ('resize_add', 'pool'):
+                graph.trunk_bwd(self, op)
             else:                                               # stem: the conv bias feeds batch norm -> zero gradient
                 _, name, src, z, y = op
                 sm, si = self.bnsave[name]
@@ -486,13 +365,7 @@ class RetinaNet(heads.BatchedInference, DetectorBase):
         self.last_accuracy = torch.zeros((), device=dev)
         self.stat_scratch = torch.zeros(2 * max(s[5] for s in self.specs), device=dev)     # the moving statistics odtk_bn_fwd updates (_bn_relu)
         self.ws = torch.zeros(self._max_ws, dtype=torch.uint8, device=dev)
-        self.wt, entries = {}, []
-        for name, cin, cout, k, _, _, _ in self.specs[1:]:
-            d = self.desc[name]
-            kp = self.acts[name].ld
-            self.wt[name] = torch.zeros(d.C * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], cout, k, k, d.C, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
+        graph.filter_table(self, self._rows(self.specs[1:]))
         if self.mode == 'train':
             self._build_backward(N, 0, dt, dev)
         self._refresh_operand_copies()

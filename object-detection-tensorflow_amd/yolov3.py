@@ -22,13 +22,11 @@ data-parallel gradient buckets of dist.py rely on).
 """
 from __future__ import annotations
 
-import math
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import heads, ops
+from . import graph, heads, ops
 from .base import DetectorBase, _Act
 from .warmup import F32Warmup
 
@@ -39,7 +37,7 @@ STRIDE = (8., 16., 32.)                                                     # :3
 LEAKY = 2                                                                   # odtk_bn_fwd activation code
 
 
-class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
+class YOLOv3(heads.BatchedInference, F32Warmup, graph.SharedGradients, DetectorBase):
     def __init__(self, config, data_provider):
         assert len(config['data_shape']) == 3
         self._prologue(config, data_provider, native_test_batch=True, num_val_optional=True)      # (this class reads num_val only with a val_generator)
@@ -71,35 +69,23 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
 
     # ------------------------------------------------------------------ parameters
     @staticmethod
+    def _rows(specs):
+        return [graph.Row(name, (cout, k, k, cin), cout, cout, True, cin * k * k) for name, cin, cout, k, _, _ in specs]
+
+    @staticmethod
     def param_layout(specs, chunk):
-        """(pinfo, nparam, sinfo, nstat): offsets of every parameter / statistic in the flat buffers, creation order (host logic,
-        no device needed: the data-parallel bucketing is tested on CPU with exactly this layout)"""
-        pinfo, sinfo = OrderedDict(), OrderedDict()
-        off = soff = 0
-        for name, cin, cout, k, _, _ in specs:
-            for suffix, shape in (('.w', (cout, k, k, ops.pad_to(cin, chunk))), ('.b', (cout,)), ('.gamma', (cout,)), ('.beta', (cout,))):
-                pinfo[name + suffix] = (off, shape)
-                off += ops.pad_to(int(np.prod(shape)), 64)
-            for suffix in ('.mmean', '.mvar'):
-                sinfo[name + suffix] = (soff, (cout,))
-                soff += ops.pad_to(cout, 64)
-        return pinfo, off, sinfo, soff
+        """(pinfo, nparam, sinfo, nstat) of graph.param_layout (host logic, no device needed: the data-parallel bucketing is tested on CPU with exactly
+        this layout)"""
+        return graph.param_layout(YOLOv3._rows(specs), chunk)
 
     def _init_parameters(self, seed):
-        self.pinfo, off, self.sinfo, soff = self.param_layout(self.specs, self.chunk)
-        self._alloc_flat(off, soff)
         # synthetic initialisation: variance-scaling kernels (:501), zero bias, BN gamma 1 / beta 0 / moving (0, 1)
-        g = torch.Generator().manual_seed(seed)
-        for name, cin, cout, k, _, _ in self.specs:
-            self.set_param(name + '.w', torch.randn(cout, k, k, cin, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-            self.param(name + '.gamma').fill_(1.0)
-            self.stat(name + '.mvar').fill_(1.0)
+        graph.init_parameters(self, self._rows(self.specs), seed)
 
     # ------------------------------------------------------------------ the graph: buffers + launch plan
     def _build(self):
         N, dev, dt = self.batch_size, self.dev, self.tdt
         H, W, _ = self.data_shape
-        self._cin = {s[0]: s[1] for s in self.specs}
         self.images = torch.zeros(N, H, W, 3, device=dev)
         c0 = ops.pad_to(3, self.chunk)
         x = _Act('input', N, H, W, 3, c0, dt, dev)
@@ -108,12 +94,7 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
         self.acts = {'input': x}
         it = iter(self.specs)
         max_ws = max_z = 0
-        groups = {}                                            # union-find over gradient groups
-
-        def find(g):
-            while groups.setdefault(g, g) != g:
-                g = groups[g]
-            return g
+        self._groups = {}                                      # union-find over gradient groups (graph.SharedGradients)
 
         def conv(src, out_f32=False):
             nonlocal max_ws, max_z
@@ -134,8 +115,8 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
         def add(a, b):
             y = _Act(f'sum{len(self.plan)}', N, a.H, a.W, a.C, a.ld, dt, dev)
             self.acts[y.name] = y
-            groups[find(b.gid)] = find(y.gid)                 # b, a and y share one gradient buffer
-            groups[find(a.gid)] = find(y.gid)
+            self.union(b, y)                                  # b, a and y share one gradient buffer
+            self.union(a, y)
             self.plan.append(('add', a, b, y))
             return y
 
@@ -165,46 +146,19 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
         E = self.num_classes + 5
         self.preds = [a.t.view(N, a.H, a.W, self.num_priors, E) for a in self.pred_acts]
         # dgrad-layout filters (every conv but the first: the input needs no gradient)
-        self.wt, entries = {}, []
-        for name, cin, cout, k, _, _ in self.specs[1:]:
-            d = self.desc[name]
-            kp = self.z[name].ld
-            self.wt[name] = torch.zeros(d.C * k * k * kp, dtype=dt, device=dev)
-            entries.append((self._flat(name + '.w', self.P), self.wt[name], cout, k, k, d.C, kp))
-        self._fp_batch = ops.FilterPrepareBatch(entries, self.DT, dev)
-        self.find = find
+        graph.filter_table(self, self._rows(self.specs[1:]))
         if self.mode == 'train':
-            # gradient buffers, one per group; the backward plan records who writes first and who accumulates
+            # gradient buffers, one per group (the prediction activations' are the views of dpreds); the backward plan records who writes first and who
+            # accumulates: a conv into its source, an upcat into `bottom` (its `lat` half is always written first)
             self.zg = torch.zeros(max_z, dtype=dt, device=dev)            # d(pre-BN conv output): lives for one layer
             self.dpreds = [torch.zeros_like(p) for p in self.preds]
-            self.g = {find(a.gid): dp.view(a.M, a.ld) for a, dp in zip(self.pred_acts, self.dpreds)}
-            written = set(self.g)
-            self.bplan = []
-            for op in reversed(self.plan):
-                if op[0] == 'conv':
-                    _, name, src, z, y, act = op
-                    assert find(y.gid) in written, name
-                    acc = find(src.gid) in written
-                    self.bplan.append(('conv', name, src, z, y, act, acc))
-                    written.add(find(src.gid))
-                elif op[0] == 'upcat':
-                    _, bottom, lat, y = op
-                    assert find(y.gid) in written
-                    self.bplan.append(('upcat', bottom, lat, y, find(bottom.gid) in written))
-                    written.add(find(bottom.gid)); written.add(find(lat.gid))
-                else:
-                    assert find(op[3].gid) in written
-            for a in self.acts.values():
-                gid = find(a.gid)
-                if gid not in self.g and gid in written and a is not self.input:
-                    self.g[gid] = torch.zeros(a.M, a.ld, dtype=dt, device=dev)
+            self.g = {self.find(a.gid): dp.view(a.M, a.ld) for a, dp in zip(self.pred_acts, self.dpreds)}
+            io = {'conv': lambda op: ([op[4]], [op[2]]), 'upcat': lambda op: ([op[3]], [op[1], op[2]]), 'add': lambda op: ([op[3]], [])}
+            self.bplan = [op + (acc,) for op, acc in self._reverse(io) if op[0] != 'add']
             self.loss_parts = torch.zeros(N, 5, device=dev)
             self.loss_ws = ops.yolov3_workspace(self.preds, N, dev)
             self.gt = None
         self._refresh_operand_copies()
-
-    def grad_of(self, act):
-        return self.g[self.find(act.gid)]
 
     # ------------------------------------------------------------------ forward / backward
     def _forward(self, training, subtract_mean=True):
@@ -222,7 +176,7 @@ class YOLOv3(heads.BatchedInference, F32Warmup, DetectorBase):
                                self.stat(name + '.mvar'), sm, si, training, act, y.t, y.ld, z.M, 0, self.ws)
             elif op[0] == 'add':
                 _, a, b, y = op
-                ops.add2d(a.t, a.ld, b.t, b.ld, y.t, y.ld, y.M, y.C)
+                ops.add2d(a.t, a.ld, b.t, b.ld, y.t, y.ld, y.M, y.C)          # (y.C where graph.trunk_fwd passes y.ld: the same number here, every sum has 64 .. 1024 channels)
             else:
                 _, bottom, lat, y = op
                 ops.add2d(bottom.t, bottom.ld, None, 0, y.t, y.ld, y.M, bottom.C)

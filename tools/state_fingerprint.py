@@ -20,11 +20,18 @@ so the second step crosses the hand-over from the f32 twin):
   backbone_loaded  a FRESH model restored from that prefix through load_pretraining_weight / load_pretrained_weight (the classes that have one): SHA-256
                  of P and of the optimizer buffers, which must be the fresh model's own, and global_step
   graph_steps .. yolov3 and refinedet on the GPU: a model built with use_graph=True after FIVE steps (two eager, the capture, two replays): loss and state
+  launches ..... every call of a plain function of odtk.ops during the two optimizer steps and the test-mode test_one_image, in order: the count and a
+                 SHA-256 over the canonical calls (`canon`: a tensor is the ordinal of the first appearance of its data_ptr -- counted per model, the
+                 trained one and the test-mode one --, dtype, shape and strides: independent of where the allocator put it; 'sha_without_ordinals': the same with the
+                 ordinals taken out); --full keeps the list itself ('calls'), to locate a difference
 The file keeps the first 64 bits of every hash.  Without --full the long tables -- the hashes of every array of export_tf_variables() and of every
 entry of the checkpoint's 'params' and 'layout' -- are folded into {'n': count, 'sha': SHA-256 over the sorted 'name:hash' lines}, so that a file stays a page long.
 """
 import argparse
+import contextlib
+import ctypes
 import hashlib
+import inspect
 import json
 import os
 import sys
@@ -53,6 +60,73 @@ def sha(t):
         return hashlib.sha256(str(t.dtype).encode() + str(tuple(t.shape)).encode() + data).hexdigest()[:HEX]
     a = np.ascontiguousarray(t)
     return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()[:HEX]
+
+
+TRACE = None        # while a list: every call through a plain function of odtk.ops is appended to it (trace_ops)
+ORDINALS = {}       # data_ptr -> ordinal of its first appearance in the trace of the model that is running (cleared when the test-mode model takes over)
+
+
+def canon(a):
+    """an argument of a traced call as JSON-able data that does not depend on addresses"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        return ['T', ORDINALS.setdefault(a.data_ptr(), len(ORDINALS)), str(a.dtype), list(a.shape), list(a.stride())]
+    if isinstance(a, ctypes.Array) and a._type_ is ctypes.c_void_p:          # a table of addresses (the per-level tensors of a loss): its elements read back as ints
+        return [canon(ctypes.c_void_p(x)) for x in a]
+    if isinstance(a, (list, tuple, ctypes.Array)):
+        return [canon(x) for x in a]
+    if isinstance(a, dict):
+        return {str(k): canon(v) for k, v in sorted(a.items(), key=lambda kv: str(kv[0]))}
+    if isinstance(a, ctypes.Structure):
+        return {'struct': type(a).__name__, 'fields': [canon(getattr(a, f[0])) for f in a._fields_]}
+    if isinstance(a, ctypes.c_void_p):                         # the real library's call layer gets raw addresses: numbered like the tensors they point into
+        return ['P', None if a.value is None else ORDINALS.setdefault(a.value, len(ORDINALS))]
+    if type(a).__name__ == 'CArgObject':                       # ctypes.byref(structure)
+        return canon(a._obj)
+    if isinstance(a, float):
+        return a.hex()
+    r = repr(a)
+    if ' at 0x' in r and hasattr(a, '__dict__'):          # a plain object (a workspace holder): its type and what it holds
+        return {'object': type(a).__name__, 'vars': canon(vars(a))}
+    return r
+
+
+def without_ordinals(x):
+    """the trace with the tensor / address ordinals taken out: what is left to compare where two runs of ONE revision number them differently"""
+    if isinstance(x, list):
+        if len(x) == 5 and x[0] == 'T':
+            return ['T'] + x[2:]
+        if len(x) == 2 and x[0] == 'P':
+            return ['P']
+        return [without_ordinals(v) for v in x]
+    return {k: without_ordinals(v) for k, v in x.items()} if isinstance(x, dict) else x
+
+
+def trace_ops():
+    """wrap the plain functions of odtk.ops (the real launches, or the CPU stand-in's once mock_ops.installed() has swapped them in): the classes call
+    `ops.name(...)` through the module, so every call lands in TRACE while it is a list"""
+    from odtk import ops
+
+    def traced(name, fn):
+        def w(*a, **k):
+            if TRACE is not None:
+                TRACE.append([name] + [canon(x) for x in a] + [[n, canon(v)] for n, v in sorted(k.items())])
+            return fn(*a, **k)
+        w.__name__ = name
+        return w
+    for name, fn in list(vars(ops).items()):
+        if inspect.isfunction(fn) and not name.startswith('_'):
+            setattr(ops, name, traced(name, fn))
+
+
+@contextlib.contextmanager
+def tracing(calls):
+    global TRACE
+    TRACE = calls
+    try:
+        yield
+    finally:
+        TRACE = None
 
 
 def build(kind, size, engine, device, mode='train', **extra):
@@ -117,8 +191,11 @@ def fingerprint(case, device):
     m, images, gt, lr = build(kind, size, engine, device, **extra)
     rec = {'class': type(m).__name__, 'engine': engine, 'size': size, 'steps': []}
     m.set_batch(images, gt)
+    calls = []
+    ORDINALS.clear()
     for _ in range(2):
-        loss = float(torch.as_tensor(m.train_step(lr)).reshape(-1)[0].item())
+        with tracing(calls):
+            loss = float(torch.as_tensor(m.train_step(lr)).reshape(-1)[0].item())
         rec['steps'].append(dict(state(m), loss=loss.hex()))
     rec['tf_variables'] = {k: sha(v) for k, v in m.export_tf_variables().items()}
     params = m.export_params()
@@ -154,13 +231,17 @@ def fingerprint(case, device):
         del g
     t, images, _, _ = build(kind, size, 'f32', device, mode='test')
     t.load_oracle_params(params)
+    ORDINALS.clear()                     # a new model: its buffers may sit where freed ones of the trained model sat, ordinals count from here again
     try:
-        scores, bbox, cid = t.test_one_image(images[:1].numpy())
+        with tracing(calls):
+            scores, bbox, cid = t.test_one_image(images[:1].numpy())
         rec['detections'] = {'n': int(len(scores)), 'scores': sha(scores), 'bbox': sha(bbox), 'class_id': sha(cid)}
     except AssertionError as e:          # the CPU stand-in has no decode / NMS launch for some classes: 'libodtk takes device pointers'
         if torch.device(device).type != 'cpu':
             raise
         rec['detections'] = {'n': -1, 'unavailable': str(e)}
+    rec['launches'] = {'n': len(calls), 'sha': hashlib.sha256(json.dumps(calls).encode()).hexdigest()[:HEX], 'calls': calls,
+                       'sha_without_ordinals': hashlib.sha256(json.dumps(without_ordinals(calls)).encode()).hexdigest()[:HEX]}
     return rec
 
 
@@ -171,6 +252,7 @@ def fold(table):
 
 def compact(rec):
     rec = dict(rec, tf_variables=fold(rec['tf_variables']), checkpoint=dict(rec['checkpoint'], hashes=dict(rec['checkpoint']['hashes'])))
+    rec['launches'] = {k: v for k, v in rec['launches'].items() if k != 'calls'}
     for k in ('params', 'layout'):
         if isinstance(rec['checkpoint']['hashes'].get(k), dict) and 'sha' not in rec['checkpoint']['hashes'][k]:
             rec['checkpoint']['hashes'][k] = fold(rec['checkpoint']['hashes'][k])
@@ -203,7 +285,6 @@ def main():
         d = diff(a, b)
         print(f'{len(d)} differing fields' + ''.join('\n  ' + p for p in d[:40]))
         sys.exit(1 if d else 0)
-    import contextlib
     import torch
     torch.set_num_threads(args.threads)
     out = json.load(open(args.out)) if args.out and os.path.exists(args.out) else {}
@@ -212,6 +293,7 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
         import mock_ops
     with (mock_ops.installed() if cpu else contextlib.nullcontext()):
+        trace_ops()
         for case in args.case or list(CASES):
             tables = contextlib.nullcontext()
             if cpu and case == 'ssd512':         # the mocked box-side launches call the oracle, which reads the swapped tables
