@@ -575,6 +575,9 @@ __global__ void __launch_bounds__(64) yolov3_pos_kernel(const YlArgs a) {
         }
         const int l = (best_iou[0] > best_iou[1] && best_iou[0] > best_iou[2]) ? 0
                       : (best_iou[1] > best_iou[0] && best_iou[1] > best_iou[2]) ? 1 : 2;     // :186-190
+        // a centre on the bottom / right image edge (or outside the picture) has no cell: the reference's gather fails there; the box is skipped, as
+        // centernet_prep_kernel and yolov2_loss_kernel do, and still counts in G
+        if (cyv[l] < 0 || cyv[l] >= a.H[l] || cxv[l] < 0 || cxv[l] >= a.W[l]) continue;
         const size_t at = (((size_t)n * a.H[l] * a.W[l] + (size_t)cyv[l] * a.W[l] + cxv[l]) * a.P + best_k[l]) * E;
         const float* p = a.pred[l] + at;
         float* d = a.d_pred[l] + at;
@@ -857,7 +860,7 @@ __global__ void __launch_bounds__(DH_THREADS) yolov2_loss_kernel(const Y2Args a)
     const float* pr = a.pred + (long long)n * img;
     float* dp = a.d_pred + (long long)n * img;
     const float* gt = a.gt + (long long)n * a.pad * 5;
-    if (tid == 0) s_G = min(first_argmin_col0(gt, a.pad), DH_MAX_GT);
+    if (tid == 0) s_G = first_argmin_col0(gt, a.pad);            // < pad <= DH_MAX_GT (odtk_yolov2_loss)
     for (long long i = tid; i < img; i += DH_THREADS) dp[i] = 0.f;
     for (int i = tid; i < cells; i += DH_THREADS) s_has[i] = 0;
     __syncthreads();
@@ -981,7 +984,8 @@ extern "C" int odtk_yolov2_loss(const float* pred, int N, int H, int W, int num_
     Y2Args a;
     memset(&a, 0, sizeof(a));
     if (int e = y2_fill(a, pred, H, W, num_priors, C, priors)) return e;
-    ODTK_REQUIRE(gt && loss_parts && d_pred && N > 0 && pad > 0, "yolov2_loss: bad argument");
+    // s_g holds DH_MAX_GT boxes: a longer list is refused, never cut short (the reference uses every box)
+    ODTK_REQUIRE(gt && loss_parts && d_pred && N > 0 && pad > 0 && pad <= DH_MAX_GT, "yolov2_loss: bad argument (pad=%d, max %d)", pad, DH_MAX_GT);
     a.gt = gt; a.N = N; a.pad = pad; a.stride = stride;
     a.coord = coord_scale; a.noobj = noobj_scale; a.obj = obj_scale; a.cls = class_scale; a.grad_scale = grad_scale;
     a.loss_parts = loss_parts; a.d_pred = d_pred;

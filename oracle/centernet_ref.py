@@ -37,7 +37,10 @@ def gaussian_radius(h, w, min_overlap=0.7):
     b3 = -2. * min_overlap * (h + w)
     c3 = (min_overlap - 1.) * w * h
     r3 = (b3 + torch.sqrt(b3 ** 2. - 4. * a3 * c3)) / 2.
-    return torch.stack([r1, r2, r3]).min()
+    r = torch.stack([r1, r2, r3])
+    if r.numel() == 0:                                      # no box: tf.reduce_min over an empty tensor is +inf (CenterNet.py:270)
+        return torch.tensor(float('inf'))
+    return r.min()
 
 
 def targets(gt, H, W, C, stride=STRIDE):

@@ -154,7 +154,10 @@ def image_loss(pred, gt, priors, scales, num_classes):
     inter2 = (torch.minimum(gg2, n_y2x2) - torch.maximum(gg1, n_y1x1)).prod(-1)
     aarea2 = (n_y2x2 - n_y1x1).prod(-1)
     garea2 = (gg2 - gg1).prod(-1)
-    agiou = (inter2 / (aarea2 + garea2 - inter2)).max(dim=1).values                    # [cells, P]
+    if G == 0:                                                                         # tf.reduce_max over the empty box axis is -inf (:169)
+        agiou = torch.full((inter2.shape[0], P), float('-inf'))
+    else:
+        agiou = (inter2 / (aarea2 + garea2 - inter2)).max(dim=1).values                # [cells, P]
     pobj_nb = pobj[..., 0][~has]
     noobj_loss = (_bce(pobj_nb, torch.zeros_like(pobj_nb)) * (agiou <= 0.6).float()).sum()
     return coord_scale * (yx_loss + hw_loss) + class_scale * class_loss + obj_scale * obj_loss + noobj_scale * noobj_loss

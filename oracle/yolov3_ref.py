@@ -95,7 +95,10 @@ def one_image_loss(preds, gt, num_classes=20, coord_scale=1., noobj_scale=1., ob
         gy1, gy2 = d['g_y1'].unsqueeze(0), d['g_y2'].unsqueeze(0)                       # [1,G,1,2]
         inter = (torch.minimum(gy2, b2) - torch.maximum(gy1, b1)).prod(-1)              # [A,G,P]
         iou = inter / ((b2 - b1).prod(-1) + (gy2 - gy1).prod(-1) - inter)
-        keep = (iou.max(dim=1).values <= 0.5).float()                                   # [A,P]
+        if G == 0:                                                                      # tf.reduce_max over the empty box axis is -inf: every prior stays
+            keep = torch.ones(iou.shape[0], iou.shape[2])
+        else:
+            keep = (iou.max(dim=1).values <= 0.5).float()                               # [A,P]
         o = p[..., C + 4].reshape(H * W, -1)[free]
         noobj = noobj + (_bce(o, torch.zeros_like(o)) * keep).sum()
     Gf = float(G)
