@@ -2,7 +2,7 @@
 """The reference's driver flow (testSSD300.py / testYOLOv3.py: config dict -> data provider -> model -> train_one_epoch ->
 save_weight -> test_one_image) on synthetic VOC-shaped pictures, with the GPU augmentor in front of the model.  After every epoch the model is
 evaluated on a held-out synthetic validation set (VOC07 mAP, model.evaluate(batch_size=...): batched inference) and saved as 'best' when the mAP improves.
-Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet] [epochs]
+Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet] [epochs] [classes]      (classes: 20 by default; 80 for a COCO-sized head)
 
 What changes for a user of the reference:
     import SSD300 as net; model = net.SSD300(config, data_provider)        ->   from odtk import SSD300
@@ -21,6 +21,7 @@ from odtk.augment import Augmentor            # noqa: E402
 
 which = sys.argv[1] if len(sys.argv) > 1 else 'ssd300'
 epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+num_classes = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 size = {'ssd300': 300, 'yolov3': 416, 'retinanet': 512}[which]
 batch_size = 8
 dev = torch.device('cuda:0')
@@ -46,7 +47,7 @@ class SyntheticVOC:
                 k = int(self.rng.integers(1, 5))
                 yc, xc = self.rng.uniform(0.3, 0.7, k) * h, self.rng.uniform(0.3, 0.7, k) * w
                 bh, bw = self.rng.uniform(0.1, 0.5, k) * h, self.rng.uniform(0.1, 0.5, k) * w
-                gts.append(torch.tensor(np.stack([yc - bh / 2, yc + bh / 2, xc - bw / 2, xc + bw / 2, self.rng.integers(0, 20, k)], 1), dtype=torch.float32))
+                gts.append(torch.tensor(np.stack([yc - bh / 2, yc + bh / 2, xc - bw / 2, xc + bw / 2, self.rng.integers(0, num_classes, k)], 1), dtype=torch.float32))
             yield self.aug(imgs, gts)
 
 
@@ -54,17 +55,17 @@ val_batches = list(SyntheticVOC(2, seed=1))      # held out: the same pictures a
 data_provider = {'data_shape': [size, size, 3], 'num_train': 4 * batch_size, 'num_val': 2 * batch_size, 'train_generator': SyntheticVOC(4),
                  'val_generator': val_batches}
 if which == 'ssd300':
-    config = {'mode': 'train', 'data_format': 'channels_last', 'num_classes': 20, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'batch_size': batch_size,
+    config = {'mode': 'train', 'data_format': 'channels_last', 'num_classes': num_classes, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'batch_size': batch_size,
               'nms_score_threshold': 0.5, 'nms_max_boxes': 20, 'nms_iou_threshold': 0.5, 'pretraining_weight': './vgg_16.ckpt'}   # testSSD300.py:15-32
     model = odtk.SSD300(config, data_provider)
 elif which == 'retinanet':
     config = {'is_bottleneck': True, 'residual_block_list': [3, 4, 6, 3], 'init_conv_filters': 16, 'mode': 'train', 'is_pretraining': False,
-              'data_shape': [size, size, 3], 'num_classes': 20, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'data_format': 'channels_last',
+              'data_shape': [size, size, 3], 'num_classes': num_classes, 'weight_decay': 1e-4, 'keep_prob': 0.5, 'data_format': 'channels_last',
               'batch_size': batch_size, 'gamma': 2.0, 'alpha': 0.25, 'nms_score_threshold': 0.8, 'nms_max_boxes': 10,
               'nms_iou_threshold': 0.45}                                                                # testretinanet.py:22-41
     model = odtk.RetinaNet(config, data_provider)
 else:
-    config = {'mode': 'train', 'data_shape': [size, size, 3], 'num_classes': 20, 'weight_decay': 5e-4, 'keep_prob': 0.5, 'data_format': 'channels_last',
+    config = {'mode': 'train', 'data_shape': [size, size, 3], 'num_classes': num_classes, 'weight_decay': 5e-4, 'keep_prob': 0.5, 'data_format': 'channels_last',
               'batch_size': batch_size, 'coord_scale': 1, 'noobj_scale': 1, 'obj_scale': 5., 'class_scale': 1., 'num_priors': 3,
               'nms_score_threshold': 0.5, 'nms_max_boxes': 10, 'nms_iou_threshold': 0.5,
               'priors': [[[10., 13.], [16, 30.], [33., 23.]], [[30., 61.], [62., 45.], [59., 119.]], [[116., 90.], [156., 198.], [373., 326.]]]}  # testYOLOv3.py:17-41

@@ -405,7 +405,8 @@ int odtk_nms_batched(const float* boxes, long long box_stride, const float* scor
 /* ---- batched inference tail (csrc/detect_batched.hip): decode -> [row compaction] -> image x class NMS -> detection pack, N images per launch ----
  *
  * Decode of N images: the arithmetic and outputs of odtk_ssd_decode / odtk_retina_decode per image (the same kernel, one y-block per image), priors /
- * anchors shared.  pred [N][A][ld] (SSD family) or pconf [N][A][C] + pbox [N][A][4] (RetinaNet); conf, cand [N][A][C-1], boxes [N][A][4], keep [N][A]. */
+ * anchors shared.  pred [N][A][ld] (SSD family) or pconf [N][A][C] + pbox [N][A][4] (RetinaNet); conf, cand [N][A][C-1], boxes [N][A][4], keep [N][A].
+ * 2 <= C <= 256 with the numerics of odtk_ssd_decode on either side of C = 32 ("Class limits" below); 1 <= N <= 65535. */
 int odtk_ssd_decode_batched(const float* pred, int N, int A, int C, int ld, const float* yx, const float* hw, float score_thr, float* conf,
                             float* boxes, unsigned char* keep, unsigned char* cand, void* stream);
 int odtk_retina_decode_batched(const float* pconf, const float* pbox, int N, int A, int C, const float* yx, const float* hw, float score_thr,
@@ -454,9 +455,26 @@ int odtk_detection_pack(const int* nms_idx, const int* nms_cnt, int N, int num_c
                         const float* boxes, long long box_istride, int* counts, int* offsets, float* scores, float* bbox, int* class_id,
                         void* stream);
 
-/* SSD300._compute_one_image_loss steps 8-12 (SSD300.py:427-453) + the batch mean
+/* ---- Class limits of the softmax box side, and the numerics on either side of them ----
+ * odtk_ssd_loss, odtk_ssd_decode, odtk_ssd_decode_batched, odtk_retina_loss, odtk_retina_decode and odtk_retina_decode_batched take rows of 2 <= C <= 256
+ * logits, the background included (255 object classes); odtk_fcos_loss takes 1 <= C <= 256 classes (no background column).  More is refused with
+ * ODTK_ERR_ARG and a message naming the limit.  The host picks the kernel from C:
+ *   C <= 32 (FCOS: C <= 64): one thread per row (FCOS: per location); the sum of exponentials adds the classes c = 0 .. C-1 in order.
+ *   C  > 32: a group of 16 adjacent lanes per row, lane j holding the classes c = j (mod 16) (csrc/wide_row.h).
+ *     - the row maximum is exact;
+ *     - the sum of exponentials is lane j's classes in ascending order, then a butterfly over the 16 lanes with offsets 8, 4, 2, 1: it differs from the
+ *       in-order sum in the last bits, and is the same bits in all 16 lanes and from run to run;
+ *     - an arg-max tie goes to the lower class index, as below 33;
+ *     - gradients reach dpred / dconf / dbox the way the one-thread kernels write them: odtk_ssd_loss adds them into the zeroed dpred with float atomics (a row
+ *       that is the best anchor of two boxes, or of one and a positive besides, is added to more than once); odtk_retina_loss stores the rows of the positive,
+ *       negative and ignored anchors and then adds the best-anchor rows with float atomics;
+ *     - every output is bit-identical from run to run wherever it is below the limit: all but the elements of rows added to three times or more.
+ *   FCOS, C > 64: the thread-per-location layout with four 64-bit words of heat-map target instead of one; the classes of a location are added in ascending
+ *   order on both sides of the limit, no atomics: bit-identical from run to run.
+ *
+ * SSD300._compute_one_image_loss steps 8-12 (SSD300.py:427-453) + the batch mean
  * (SSD300.py:148) and its gradient.  loss_parts[N][4] = {neg, pos_conf, coord, total};
- * dpred [N][A][ld] is overwritten with d(sum_i total_i * grad_scale)/dpred. */
+ * dpred [N][A][ld] is overwritten with d(sum_i total_i * grad_scale)/dpred.  2 <= C <= 256 (background = C-1), ld >= C + 4. */
 int odtk_ssd_loss(const float* pred, int N, int A, int C, int ld, const float* yx, const float* hw,
                   const float* gt, int P, const int* ngt, const int* best,
                   const unsigned char* status, const int* rgindex, const int* counts,
@@ -464,7 +482,8 @@ int odtk_ssd_loss(const float* pred, int N, int A, int C, int ld, const float* y
                   float grad_scale, float* loss_parts, float* dpred, void* stream);
 
 /* Inference decode (SSD300.py:157-171): softmax, drop rows whose arg-max is background,
- * decode boxes.  conf [A][C-1], boxes [A][4]; cand[A][C-1] u8 = keep && conf >= thr. */
+ * decode boxes.  conf [A][C-1], boxes [A][4]; cand[A][C-1] u8 = keep && conf >= thr.  2 <= C <= 256, ld >= C + 4; the arg-max is taken over the
+ * probabilities, first maximum ("Class limits" above: C > 32 runs a 16-lane group per row, its sum of exponentials in the order stated there). */
 int odtk_ssd_decode(const float* pred0, int A, int C, int ld, const float* yx, const float* hw,
                     float score_thr, float* conf, float* boxes, unsigned char* keep,
                     unsigned char* cand, void* stream);
@@ -512,7 +531,9 @@ int odtk_refinedet_decode(const float* arm_loc, const float* arm_conf, const flo
 /* Focal (softmax flavour, alpha on positives AND negatives, p clipped to [1e-8, 1], sum / #positives;
  * RetinaNet.py:457-474) + smooth-L1 on the positive rows (:441-446).  pconf [N][A][C] logits (background =
  * class C-1), pbox [N][A][4] = (ty, tx, th, tw).  loss_parts[N][2] = {focal, coord}; dconf / dbox are
- * overwritten with d(sum_i (focal_i + coord_i) * grad_scale) / d(pconf, pbox)  (grad_scale = 1 / batch). */
+ * overwritten with d(sum_i (focal_i + coord_i) * grad_scale) / d(pconf, pbox)  (grad_scale = 1 / batch).  2 <= C <= 256, P <= 128.  C > 32 ("Class
+ * limits" above): a 16-lane group per row, rows staged through 32 KiB of LDS in tiles of 128 / 64 / 32 rows for C <= 64 / 128 / 256; the loss is the sum
+ * of one partial per 512 rows in row order, then the best-anchor rows. */
 int odtk_retina_loss(const float* pconf, const float* pbox, int N, int A, int C, const float* yx,
                      const float* hw, const float* gt, int P, const int* ngt, const int* best,
                      const unsigned char* status, const int* rgindex, const int* counts, float alpha,
@@ -530,7 +551,7 @@ int odtk_gap_softmax_ce_fwd(const void* x, int dtype, int N, int HW, int C, int 
                             float* logits, float* loss, int* pred, float* correct, float* dlogits, void* stream);
 int odtk_gap_softmax_ce_bwd(const float* dlogits, int N, int HW, int C, void* dx, int dtype, int lddx, int accumulate, void* stream);
 /* RetinaNet inference branch up to the per-class NMS loop (RetinaNet.py:224-238): softmax, background-arg-max mask,
- * box decode; outputs as odtk_ssd_decode (conf [A][C-1], boxes [A][4] y1,x1,y2,x2, keep [A], cand [A][C-1]). */
+ * box decode; outputs as odtk_ssd_decode (conf [A][C-1], boxes [A][4] y1,x1,y2,x2, keep [A], cand [A][C-1]), the same kernels: 2 <= C <= 256. */
 int odtk_retina_decode(const float* pconf, const float* pbox, int A, int C, const float* yx, const float* hw,
                        float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand,
                        void* stream);
@@ -556,7 +577,8 @@ int odtk_centernet_decode(const float* keypoints, const float* offset, const flo
  * (FCOS.py:153-189, :266-348) and the decode candidates (FCOS.py:197-246; feed them to odtk_nms_batched).
  * conf / reg / center: host arrays of 5 device pointers (p3..p7) to [N][H_l][W_l][C] logits, [..][4] = l,r,t,b
  * distances (> 0, i.e. after the exp), [..][1] centre-ness logits; shapes [5][2] = H_l, W_l; strides 8..128.
- * loss [N] per image; d_* as for CenterNet.  workspace: odtk_fcos_workspace_bytes. */
+ * loss [N] per image; d_* as for CenterNet.  workspace: odtk_fcos_workspace_bytes.  odtk_fcos_loss: 1 <= C <= 256, P <= 128 ("Class limits" above: the
+ * results for C <= 64 are those of the one-word kernel, unchanged). */
 long long odtk_fcos_workspace_bytes(const int* shapes, int N);
 int odtk_fcos_loss(const float* const* conf, const float* const* reg, const float* const* center, const int* shapes,
                    const float* gt, int N, int C, int P, float grad_scale, float* loss, float* const* d_conf,

@@ -10,6 +10,7 @@
 // Reference: SSD300.py:323-343 (_get_abbox), :345-453 (_compute_one_image_loss),
 // :157-190 (inference branch); tf.image.non_max_suppression == NonMaxSuppressionV3 (TF 1.13).
 #include "common.h"
+#include "wide_row.h"
 #include <math.h>
 
 namespace odtk {
@@ -844,6 +845,96 @@ __global__ void __launch_bounds__(64) ssd_loss_final_kernel(const LossArgs a) {
     o[0] = neg; o[1] = pc; o[2] = co; o[3] = neg + pc + co;
 }
 
+// ---- rows of 33 .. wr::MAXC logits (wide_row.h): ssd_loss_kernel with a 16-lane group where it has a thread.  Same grid, same split of the work over the
+// LOSS_SPLIT workgroups of an image (group q of 16 takes what thread q of 256 takes there, every 16th instead of every 256th), same a.parts and the same
+// ssd_loss_final_kernel behind it.  The loops have workgroup-uniform trip counts and switch rows off with `on`: every lane reaches every shuffle.
+constexpr int LOSS_GROUPS = LOSS_THREADS / wr::L;
+
+// softmax of row `row`, (softmax - onehot(label)) * gsc added into dpred; m, s: the row's maximum and sum of exponentials
+template <int K>
+__device__ __forceinline__ void wide_ce_row(const LossArgs& a, size_t row, int j, bool on, int label, float gsc, float& m, float& s) {
+    const float* z = a.pred + row * a.ld;
+    float* dz = a.dpred + row * a.ld;
+    float v[K];
+    wr::load<K>(z, a.C, j, on, v);
+    wr::softmax<K>(v, a.C, j, on, m, s);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = j + wr::L * k;
+        if (on && c < a.C) atomicAdd(dz + c, (v[k] / s - (c == label ? 1.f : 0.f)) * gsc);
+    }
+}
+
+// positive_row for a group: the group's first lane carries the two sums and the four coordinates
+template <int K>
+__device__ __forceinline__ void wide_positive_row(const LossArgs& a, int n, int anchor, int g, float inv_np, int j, bool on, float& ce_sum, float& coord_sum) {
+    const size_t row = (size_t)n * a.A + anchor;
+    const float* gb = a.gt + ((size_t)n * a.P + g) * 5;
+    const int label = on ? (int)gb[4] : 0;
+    const float gsc = a.grad_scale * inv_np;
+    float m, s;
+    wide_ce_row<K>(a, row, j, on, label, gsc, m, s);
+    if (!on || j != 0) return;
+    const float* z = a.pred + row * a.ld;
+    float* dz = a.dpred + row * a.ld;
+    ce_sum += logf(s) - (z[label] - m);
+    const float ayx[2] = {a.yx[2 * anchor], a.yx[2 * anchor + 1]};
+    const float ahw[2] = {a.hw[2 * anchor], a.hw[2 * anchor + 1]};
+    float cl = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float t = k < 2 ? (gb[k] - ayx[k]) / ahw[k] : logf(gb[k] / ahw[k - 2]);      // SSD300.py:446-447
+        const float d = z[a.C + k] - t;
+        const float ad = fabsf(d);
+        cl += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+        atomicAdd(dz + a.C + k, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * gsc);
+    }
+    coord_sum += cl;
+}
+
+template <int K>
+__global__ void __launch_bounds__(LOSS_THREADS) ssd_loss_wide_kernel(const LossArgs a) {
+    __shared__ float sm[LOSS_THREADS / 64];
+    const int n = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, j = tid & (wr::L - 1), q = tid / wr::L;
+    const int G = a.ngt[n];
+    const int num_pos = a.counts[n * 4 + 0];
+    const int nsel = a.sel_cnt[n];
+    const int bg = a.C - 1;
+    float neg_sum = 0.f;
+    const float inv_ns = 1.f / (float)nsel;
+    for (int i0 = s; i0 < nsel; i0 += LOSS_SPLIT * LOSS_GROUPS) {
+        const int i = i0 + LOSS_SPLIT * q;
+        const bool on = i < nsel;
+        const int anchor = on ? a.sel_idx[(size_t)n * a.sel_cap + i] : 0;
+        if (on && j == 0) neg_sum += a.negloss[(size_t)n * a.A + anchor];
+        float m, sum;
+        wide_ce_row<K>(a, (size_t)n * a.A + anchor, j, on, bg, a.grad_scale * inv_ns, m, sum);
+    }
+    float ce_sum = 0.f, coord_sum = 0.f;
+    const float inv_np = 1.f / (float)num_pos;
+    if (s == 0)
+        for (int g0 = 0; g0 < G; g0 += LOSS_GROUPS) {
+            const int g = g0 + q;
+            const bool on = g < G;
+            wide_positive_row<K>(a, n, on ? a.best[(size_t)n * a.P + g] : 0, on ? g : 0, inv_np, j, on, ce_sum, coord_sum);
+        }
+    const int per = (a.A + LOSS_SPLIT - 1) / LOSS_SPLIT;
+    const int a1 = min(a.A, (s + 1) * per);
+    for (int r0 = s * per; r0 < a1; r0 += LOSS_GROUPS) {
+        const int anchor = r0 + q;
+        const bool on = anchor < a1 && a.status[(size_t)n * a.A + anchor] == 1;
+        if (!__any(on)) continue;                              // (wave-uniform: positives are a few rows per image)
+        wide_positive_row<K>(a, n, on ? anchor : 0, on ? a.rgindex[(size_t)n * a.A + anchor] : 0, inv_np, j, on, ce_sum, coord_sum);
+    }
+    neg_sum = block_sum(neg_sum, sm);
+    ce_sum = block_sum(ce_sum, sm);
+    coord_sum = block_sum(coord_sum, sm);
+    if (tid == 0) {
+        float* o = a.parts + ((size_t)n * LOSS_SPLIT + s) * 3;
+        o[0] = neg_sum; o[1] = ce_sum; o[2] = coord_sum;
+    }
+}
+
 // ------------------------------------------------------------------ inference decode
 // `box` / `ldb`: the 4 box regressions of anchor a are box[a * ldb .. +3] (SSD300: pred + C with the row pitch of
 // pred; RetinaNet: its own [A][4] tensor)
@@ -882,6 +973,59 @@ __global__ void ssd_decode_kernel(const float* __restrict__ pred_all, long long 
         conf[(size_t)a * (C - 1) + c] = e[c];
         cand[(size_t)a * (C - 1) + c] = (kp && e[c] >= thr) ? 1 : 0;
     }
+    const float ah = hw[2 * a], aw = hw[2 * a + 1];
+    const float cy = zb[0] * ah + yx[2 * a], cx = zb[1] * aw + yx[2 * a + 1];
+    const float h = ah * expf(zb[2]), w = aw * expf(zb[3]);
+    boxes[4 * a + 0] = cy - h / 2.f; boxes[4 * a + 1] = cx - w / 2.f;
+    boxes[4 * a + 2] = cy + h / 2.f; boxes[4 * a + 3] = cx + w / 2.f;
+}
+
+
+// ssd_decode_kernel for rows of 33 .. wr::MAXC logits: a 16-lane group per row (wide_row.h), 16 rows per workgroup; the box is the first lane's, in the
+// arithmetic of the narrow kernel
+constexpr int DECODE_WIDE_THREADS = 256;
+template <int K>
+__global__ void __launch_bounds__(DECODE_WIDE_THREADS) ssd_decode_wide_kernel(const float* __restrict__ pred_all, long long pred_istride, int A, int C, int ld,
+                                                                             const float* __restrict__ box_all, long long box_istride, int ldb,
+                                                                             const float* __restrict__ yx, const float* __restrict__ hw, float thr,
+                                                                             float* __restrict__ conf_all, float* __restrict__ boxes_all,
+                                                                             unsigned char* __restrict__ keep_all, unsigned char* __restrict__ cand_all) {
+    const int j = threadIdx.x & (wr::L - 1);
+    const int row = blockIdx.x * (DECODE_WIDE_THREADS / wr::L) + threadIdx.x / wr::L;
+    const bool on = row < A;
+    const int a = on ? row : A - 1;
+    const size_t img = blockIdx.y;
+    const float* z = pred_all + img * pred_istride + (size_t)a * ld;
+    float v[K], m, s;
+    wr::load<K>(z, C, j, on, v);
+    wr::softmax<K>(v, C, j, on, m, s);
+    int arg = 0; float best = -1.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = j + wr::L * k;
+        if (c < C) {
+            const float p = v[k] / s;
+            v[k] = p;
+            if (p > best) { best = p; arg = c; }
+        }
+    }
+    wr::group_argmax(best, arg);
+    if (!on) return;
+    const bool kp = arg < C - 1;
+    float* conf = conf_all + (img * (size_t)A + a) * (C - 1);
+    unsigned char* cand = cand_all + (img * (size_t)A + a) * (C - 1);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = j + wr::L * k;
+        if (c < C - 1) {
+            conf[c] = v[k];
+            cand[c] = (kp && v[k] >= thr) ? 1 : 0;
+        }
+    }
+    if (j != 0) return;
+    keep_all[img * (size_t)A + a] = kp ? 1 : 0;
+    const float* zb = box_all + img * box_istride + (size_t)a * ldb;
+    float* boxes = boxes_all + img * (size_t)A * 4;
     const float ah = hw[2 * a], aw = hw[2 * a + 1];
     const float cy = zb[0] * ah + yx[2 * a], cx = zb[1] * aw + yx[2 * a + 1];
     const float h = ah * expf(zb[2]), w = aw * expf(zb[3]);
@@ -1053,8 +1197,14 @@ int nms_image_class_launch(const float* boxes, long long box_istride, const floa
 // the decode launch of odtk_ssd_decode / odtk_retina_decode for N images (csrc/detect_batched.hip)
 int decode_launch(const float* pred, long long pred_istride, int N, int A, int C, int ld, const float* box, long long box_istride, int ldb, const float* yx,
                   const float* hw, float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream) {
-    hipLaunchKernelGGL(ssd_decode_kernel, dim3(ceil_div(A, 256), N), dim3(256), 0, (hipStream_t)stream, pred, pred_istride, A, C, ld, box, box_istride, ldb, yx,
-                       hw, score_thr, conf, boxes, keep, cand);
+    if (C <= MAXC) {
+        hipLaunchKernelGGL(ssd_decode_kernel, dim3(ceil_div(A, 256), N), dim3(256), 0, (hipStream_t)stream, pred, pred_istride, A, C, ld, box, box_istride, ldb,
+                           yx, hw, score_thr, conf, boxes, keep, cand);
+    } else {                                                 // 33 .. wr::MAXC logits (the callers check the upper limit): a 16-lane group per row
+        const dim3 grid(ceil_div(A, DECODE_WIDE_THREADS / wr::L), N), block(DECODE_WIDE_THREADS);
+        ODTK_WIDE_SLOTS(C, K, hipLaunchKernelGGL(ssd_decode_wide_kernel<K>, grid, block, 0, (hipStream_t)stream, pred, pred_istride, A, C, ld, box, box_istride,
+                                                 ldb, yx, hw, score_thr, conf, boxes, keep, cand));
+    }
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }
@@ -1087,7 +1237,7 @@ extern "C" int odtk_ssd_loss(const float* pred, int N, int A, int C, int ld, con
                              float grad_scale, float* loss_parts, float* dpred, void* stream) {
     ODTK_REQUIRE(pred && yx && hw && gt && ngt && best && status && rgindex && counts && negloss && sel_idx &&
                  sel_cnt && loss_parts && dpred, "ssd_loss: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= MAXC && ld >= C + 4, "ssd_loss: C=%d ld=%d unsupported", C, ld);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && ld >= C + 4, "ssd_loss: C=%d ld=%d unsupported (2 <= C <= %d, ld >= C + 4)", C, ld, wr::MAXC);
     hipStream_t st = (hipStream_t)stream;
     if (int e = zero_async(dpred, (size_t)N * A * ld * sizeof(float), st)) return e;
     LossArgs a;
@@ -1096,7 +1246,8 @@ extern "C" int odtk_ssd_loss(const float* pred, int N, int A, int C, int ld, con
     a.negloss = negloss; a.sel_idx = sel_idx; a.sel_cap = sel_cap; a.sel_cnt = sel_cnt;
     a.grad_scale = grad_scale; a.loss_parts = loss_parts; a.dpred = dpred;
     if (int e = loss_scratch(N, &a.parts)) return e;
-    hipLaunchKernelGGL(ssd_loss_kernel, dim3(N, LOSS_SPLIT), dim3(LOSS_THREADS), 0, st, a);
+    if (C <= MAXC) hipLaunchKernelGGL(ssd_loss_kernel, dim3(N, LOSS_SPLIT), dim3(LOSS_THREADS), 0, st, a);
+    else ODTK_WIDE_SLOTS(C, K, hipLaunchKernelGGL(ssd_loss_wide_kernel<K>, dim3(N, LOSS_SPLIT), dim3(LOSS_THREADS), 0, st, a));
     hipLaunchKernelGGL(ssd_loss_final_kernel, dim3(ceil_div(N, 64)), dim3(64), 0, st, a);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
@@ -1106,7 +1257,7 @@ extern "C" int odtk_ssd_decode(const float* pred0, int A, int C, int ld, const f
                                float score_thr, float* conf, float* boxes, unsigned char* keep,
                                unsigned char* cand, void* stream) {
     ODTK_REQUIRE(pred0 && yx && hw && conf && boxes && keep && cand, "ssd_decode: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= MAXC && ld >= C + 4, "ssd_decode: C=%d ld=%d unsupported", C, ld);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && ld >= C + 4, "ssd_decode: C=%d ld=%d unsupported (2 <= C <= %d, ld >= C + 4)", C, ld, wr::MAXC);
     return decode_launch(pred0, 0, 1, A, C, ld, pred0 + C, 0, ld, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }
 
@@ -1115,6 +1266,6 @@ extern "C" int odtk_retina_decode(const float* pconf, const float* pbox, int A, 
                                   float score_thr, float* conf, float* boxes, unsigned char* keep, unsigned char* cand,
                                   void* stream) {
     ODTK_REQUIRE(pconf && pbox && yx && hw && conf && boxes && keep && cand, "retina_decode: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= MAXC && A > 0, "retina_decode: C=%d A=%d unsupported", C, A);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && A > 0, "retina_decode: C=%d A=%d unsupported (2 <= C <= %d)", C, A, wr::MAXC);
     return decode_launch(pconf, 0, 1, A, C, C, pbox, 0, 4, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }

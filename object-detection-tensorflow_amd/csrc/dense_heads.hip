@@ -416,6 +416,126 @@ __global__ void __launch_bounds__(DH_THREADS) fcos_level_kernel(const FcArgs a) 
     }
 }
 
+// ---- 65 .. FC_MAXC classes.  What limits fcos_level_kernel is the heat-map target of a location, one bit per class in ONE 64-bit word; there is no
+// per-row register array and no row reduction (independent sigmoids), so the wide form keeps the thread-per-location layout and carries FC_WORDS = 4 words.
+// The words are only ever indexed by unrolled compile-time values; the classes are visited in ascending order as above, so the sums are those the narrow
+// kernel would form.
+constexpr int FC_WORDS = 4, FC_MAXC = 64 * FC_WORDS;
+struct FcTargetW { float dl, dr, dt, db, loc; unsigned long long hm[FC_WORDS]; };
+
+__device__ __forceinline__ FcTargetW fcos_target_wide(const FcGt* sg, int M, float gy, float gx) {
+    FcTargetW t;
+#pragma unroll
+    for (int w = 0; w < FC_WORDS; ++w) t.hm[w] = 0ull;
+    float amin = INFINITY;
+    bool any = false;
+    for (int g = 0; g < M; ++g) {
+        const float dl = gx - sg[g].x1, dr = sg[g].x2 - gx, dt = gy - sg[g].y1, db = sg[g].y2 - gy;
+        if (dt > 0.f && db > 0.f && dl > 0.f && dr > 0.f) {
+            any = true;
+#pragma unroll
+            for (int w = 0; w < FC_WORDS; ++w) t.hm[w] |= (sg[g].cls >> 6) == w ? 1ull << (sg[g].cls & 63) : 0ull;
+            amin = fminf(amin, (dl + dr) * (dt + db));
+        }
+    }
+    t.loc = any ? 1.f : 0.f;
+    t.dl = t.dr = t.dt = t.db = 0.f;
+    if (any)
+        for (int g = 0; g < M; ++g) {
+            const float dl = gx - sg[g].x1, dr = sg[g].x2 - gx, dt = gy - sg[g].y1, db = sg[g].y2 - gy;
+            if (dt > 0.f && db > 0.f && dl > 0.f && dr > 0.f && (dl + dr) * (dt + db) == amin) {
+                t.dl = fmaxf(t.dl, dl); t.dr = fmaxf(t.dr, dr); t.dt = fmaxf(t.dt, dt); t.db = fmaxf(t.db, db);
+            }
+        }
+    return t;
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(DH_THREADS) fcos_level_wide_kernel(const FcArgs a) {
+    __shared__ FcGt sg[DH_MAX_GT];
+    __shared__ float red[DH_THREADS / 64];
+    const int n = blockIdx.y;
+    int l = 0;
+    while (l + 1 < FC_LEVELS && (int)blockIdx.x >= a.boff[l + 1]) ++l;
+    const int b = blockIdx.x - a.boff[l];
+    const int M = fcos_stage_gt(a, n, l, sg);
+    const int H = a.H[l], W = a.W[l], C = a.C, HW = H * W;
+    const int p = b * DH_THREADS + threadIdx.x;
+    const bool live = p < HW;
+    float s_iou = 0.f, s_heat = 0.f, s_cen = 0.f, s_hm = 0.f;
+    float inv = 0.f;
+    if (PASS == 1) inv = M > 0 ? a.grad_scale / a.lsum[((size_t)n * FC_LEVELS + l) * 4 + 3] : 0.f;
+    if (live && (M > 0 || PASS == 1)) {
+        const size_t px = (size_t)n * HW + p;
+        if (M == 0) {                                   // level without boxes: contributes 0 (tf.cond, FCOS.py:165-188)
+            for (int c = 0; c < C; ++c) a.d_conf[l][px * C + c] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a.d_reg[l][px * 4 + k] = 0.f;
+            a.d_center[l][px] = 0.f;
+        } else {
+            const int y = p / W, x = p - y * W;
+            const FcTargetW t = fcos_target_wide(sg, M, (float)y, (float)x);
+            const float4 pr = *reinterpret_cast<const float4*>(a.reg[l] + px * 4);      // l, r, t, b
+            const float mnl = fminf(t.dl, pr.x), mnr = fminf(t.dr, pr.y), mnt = fminf(t.dt, pr.z), mnb = fminf(t.db, pr.w);
+            const float iw = mnl + mnr, ih = mnt + mnb;
+            const float inter = iw * ih;
+            const float ag = (t.dl + t.dr) * (t.dt + t.db), ap = (pr.x + pr.y) * (pr.z + pr.w);
+            const float uni = ag + ap - inter;
+            const float iou = inter / (uni + 1e-12f);
+            const float lrmin = fminf(t.dl, t.dr), tbmin = fminf(t.dt, t.db), lrmax = fmaxf(t.dl, t.dr), tbmax = fmaxf(t.dt, t.db);
+            const float cgt = sqrtf(lrmin * tbmin / (lrmax * tbmax + 1e-12f));
+            const float cx = a.center[l][px];
+            if (PASS == 0) {
+                s_iou = -logf(iou + 1e-12f) * t.loc;
+                s_cen = fmaxf(cx, 0.f) - cx * cgt + log1pf(expf(-fabsf(cx)));
+#pragma unroll
+                for (int w = 0; w < FC_WORDS; ++w) {
+                    const unsigned long long hm = t.hm[w];
+                    for (int c = 64 * w; c < min(C, 64 * (w + 1)); ++c) {
+                        const float k = a.conf[l][px * C + c];
+                        const float s = sigmoidf_(k), ls = log_sigmoidf_(k), om = 1.f - s;
+                        if ((hm >> (c - 64 * w)) & 1ull) { s_heat += -.25f * (om * om) * ls; s_hm += 1.f; }
+                        else s_heat += -.25f * (s * s) * (-k + ls);
+                    }
+                }
+            } else {
+                float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (t.loc > 0.f) {
+                    const float den = uni + 1e-12f;
+                    const float k0 = -1.f / (iou + 1e-12f) / (den * den);
+                    const float dI[4] = {pr.x < t.dl ? ih : 0.f, pr.y < t.dr ? ih : 0.f, pr.z < t.dt ? iw : 0.f, pr.w < t.db ? iw : 0.f};
+                    const float dA[4] = {pr.z + pr.w, pr.z + pr.w, pr.x + pr.y, pr.x + pr.y};
+                    float* gp = reinterpret_cast<float*>(&g);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gp[k] = k0 * (dI[k] * den - inter * (dA[k] - dI[k])) * inv;
+                }
+                *reinterpret_cast<float4*>(a.d_reg[l] + px * 4) = g;
+                a.d_center[l][px] = (sigmoidf_(cx) - cgt) * inv;
+#pragma unroll
+                for (int w = 0; w < FC_WORDS; ++w) {
+                    const unsigned long long hm = t.hm[w];
+                    for (int c = 64 * w; c < min(C, 64 * (w + 1)); ++c) {
+                        const float k = a.conf[l][px * C + c];
+                        const float s = sigmoidf_(k), ls = log_sigmoidf_(k), om = 1.f - s;
+                        float gr;
+                        if ((hm >> (c - 64 * w)) & 1ull) gr = .25f * (2.f * s * om * om * ls - om * om * om);
+                        else gr = -.25f * (2.f * s * s * om * (-k + ls) - s * s * s);
+                        a.d_conf[l][px * C + c] = gr * inv;
+                    }
+                }
+            }
+        }
+    }
+    if (PASS == 0) {
+        const float t0 = block_sum<DH_THREADS>(s_iou, red), t1 = block_sum<DH_THREADS>(s_heat, red);
+        const float t2 = block_sum<DH_THREADS>(s_cen, red), t3 = block_sum<DH_THREADS>(s_hm, red);
+        if (threadIdx.x == 0) {
+            float* o = a.parts + ((size_t)n * a.boff[FC_LEVELS] + blockIdx.x) * 4;
+            o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
+        }
+    }
+}
+
 // per (image, level) sums in workgroup order; loss[n] = sum over active levels of (iou + heat + centre) / sum(hm)
 __global__ void __launch_bounds__(64) fcos_reduce_kernel(const FcArgs a) {
     __shared__ FcGt sg[DH_MAX_GT];
@@ -722,7 +842,8 @@ extern "C" int odtk_fcos_loss(const float* const* conf, const float* const* reg,
                               const float* gt, int N, int C, int P, float grad_scale, float* loss, float* const* d_conf,
                               float* const* d_reg, float* const* d_center, void* workspace, void* stream) {
     ODTK_REQUIRE(conf && reg && center && shapes && gt && loss && d_conf && d_reg && d_center && workspace, "fcos_loss: null pointer");
-    ODTK_REQUIRE(N > 0 && C > 0 && C <= DH_MAXC && P > 0 && P <= DH_MAX_GT, "fcos_loss: N=%d C=%d P=%d out of range", N, C, P);
+    ODTK_REQUIRE(N > 0 && C > 0 && C <= FC_MAXC && P > 0 && P <= DH_MAX_GT, "fcos_loss: N=%d C=%d P=%d out of range (C <= %d, P <= %d)", N, C, P, FC_MAXC,
+                 DH_MAX_GT);
     FcArgs a;
     memset(&a, 0, sizeof(a));
     if (int e = fcos_fill(a, shapes, N, C, P)) return e;
@@ -735,9 +856,12 @@ extern "C" int odtk_fcos_loss(const float* const* conf, const float* const* reg,
     a.parts = (float*)workspace;
     a.lsum = a.parts + (size_t)N * a.boff[FC_LEVELS] * 4;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(fcos_level_kernel<0>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
+    const bool wide = C > DH_MAXC;                       // more classes than one 64-bit heat-map word holds
+    if (wide) hipLaunchKernelGGL(fcos_level_wide_kernel<0>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(fcos_level_kernel<0>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
     hipLaunchKernelGGL(fcos_reduce_kernel, dim3(N), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(fcos_level_kernel<1>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
+    if (wide) hipLaunchKernelGGL(fcos_level_wide_kernel<1>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(fcos_level_kernel<1>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }

@@ -5,6 +5,7 @@
 // CenterNet (peak test + top-k, no NMS) and RefineDet / PFPNetR (two-stage decode, then the tail above) come in the same way: centernet_decode_launch of
 // dense_heads.hip and refinedet_decode_launch of refinedet.hip with N images.
 #include "common.h"
+#include "wide_row.h"
 
 namespace odtk {
 namespace {
@@ -127,7 +128,7 @@ using namespace odtk;
 extern "C" int odtk_ssd_decode_batched(const float* pred, int N, int A, int C, int ld, const float* yx, const float* hw, float score_thr, float* conf,
                                        float* boxes, unsigned char* keep, unsigned char* cand, void* stream) {
     ODTK_REQUIRE(pred && yx && hw && conf && boxes && keep && cand, "ssd_decode_batched: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= 32 && ld >= C + 4, "ssd_decode_batched: C=%d ld=%d unsupported", C, ld);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && ld >= C + 4, "ssd_decode_batched: C=%d ld=%d unsupported (2 <= C <= %d, ld >= C + 4)", C, ld, wr::MAXC);
     ODTK_REQUIRE(N > 0 && N <= 65535 && A > 0, "ssd_decode_batched: N=%d A=%d out of range", N, A);
     return decode_launch(pred, (long long)A * ld, N, A, C, ld, pred + C, (long long)A * ld, ld, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }
@@ -135,7 +136,7 @@ extern "C" int odtk_ssd_decode_batched(const float* pred, int N, int A, int C, i
 extern "C" int odtk_retina_decode_batched(const float* pconf, const float* pbox, int N, int A, int C, const float* yx, const float* hw, float score_thr,
                                           float* conf, float* boxes, unsigned char* keep, unsigned char* cand, void* stream) {
     ODTK_REQUIRE(pconf && pbox && yx && hw && conf && boxes && keep && cand, "retina_decode_batched: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= 32 && A > 0, "retina_decode_batched: C=%d A=%d unsupported", C, A);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && A > 0, "retina_decode_batched: C=%d A=%d unsupported (2 <= C <= %d)", C, A, wr::MAXC);
     ODTK_REQUIRE(N > 0 && N <= 65535, "retina_decode_batched: N=%d out of range", N);
     return decode_launch(pconf, (long long)A * C, N, A, C, C, pbox, (long long)A * 4, 4, yx, hw, score_thr, conf, boxes, keep, cand, stream);
 }

@@ -9,6 +9,7 @@
 // Everything that produces an INDEX follows the float32 operation order of the graph (this file is compiled
 // with -ffp-contract=off and uses IEEE division) so indices are bit-identical to the CPU oracle.
 #include "common.h"
+#include "wide_row.h"
 #include <math.h>
 namespace odtk { namespace cv { int misc_scratch(size_t bytes, hipStream_t st, char** out); } }      // conv_v3.hip: per-(device, slot) arena
 
@@ -375,6 +376,168 @@ __global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_kernel(const RLoss
     }
 }
 
+// ---- rows of 33 .. wr::MAXC logits (wide_row.h): a 16-lane group per row where the kernels above have a thread.
+// Staging as in retina_loss_kernel (16-byte global accesses from the first aligned element, the LDS image keeps the global phase, gradients leave in place),
+// but the tile is RW_LDS_FLOATS / C rows instead of 256: 128 rows up to 64 logits, 64 up to 128, 32 up to 256 -- 32 KiB of LDS per workgroup whatever C is,
+// four workgroups per CU (the workgroup declares 32 800 bytes with its reduction words; a CU has 160 KiB).  A workgroup takes RW_ROWS = 512 rows in tiles, so the partial sums (a.parts) are one pair per 512 rows.
+constexpr int RW_LDS_FLOATS = 8192, RW_ROWS = 512, RW_GROUPS = RL_THREADS / wr::L;
+
+// focal_row for a group: z / dz are the row's (LDS or global); every lane returns the row's loss (0 with the row switched off)
+template <int K>
+__device__ __forceinline__ float focal_row_wide(const RLossArgs& a, const float* z, float* dz, int label, float scale, bool add, int j, bool on) {
+    float v[K], m, s;
+    wr::load<K>(z, a.C, j, on, v);
+    wr::softmax<K>(v, a.C, j, on, m, s);
+    float el = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) el = j + wr::L * k == label ? v[k] : el;
+    el = wr::group_sum(el);                             // one lane holds it, fifteen hold 0: exact
+    if (!on) return 0.f;
+    const float inv = 1.f / s;
+    const float pu = el * inv;
+    const float pt = fminf(fmaxf(pu, 1e-8f), 1.f);
+    const float om = 1.f - pt;
+    const float lg = logf(pt);
+    const float loss = -a.alpha * powf(om, a.gamma) * lg;
+    float dpt = 0.f;
+    if (pu >= 1e-8f) dpt = a.alpha * (a.gamma * powf(om, a.gamma - 1.f) * lg - powf(om, a.gamma) / pt);
+    const float kk = dpt * pu * scale;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = j + wr::L * k;
+        if (c < a.C) {
+            const float g = kk * ((c == label ? 1.f : 0.f) - v[k] * inv);
+            if (add) atomicAdd(dz + c, g); else dz[c] = g;
+        }
+    }
+    return loss;
+}
+
+template <int K>
+__global__ void __launch_bounds__(RL_THREADS) retina_loss_wide_kernel(const RLossArgs a) {
+    __shared__ float s_red[2][RL_THREADS / 64];
+    __shared__ __attribute__((aligned(16))) float s_z[RW_LDS_FLOATS];
+    constexpr int TILE = RW_LDS_FLOATS / (wr::L * K);       // rows per tile: TILE * C <= RW_LDS_FLOATS for every C this K serves
+    const int n = blockIdx.y, tid = threadIdx.x, j = tid & (wr::L - 1), q = tid / wr::L;
+    const int num_pos = a.counts[n * 4 + 0];
+    const float inv_np = 1.f / (float)num_pos;
+    const float gs = a.grad_scale * inv_np;
+    float conf = 0.f, coord = 0.f;
+    const int wg0 = blockIdx.x * RW_ROWS, wg1 = min(a.A, wg0 + RW_ROWS);
+    for (int a0 = wg0; a0 < wg1; a0 += TILE) {
+        const int rows = min(TILE, wg1 - a0);
+        const size_t base = ((size_t)n * a.A + a0) * a.C;
+        const int nflt = rows * a.C;
+        const int head = min(nflt, (int)((4 - (base & 3)) & 3));
+        const int nvec = (nflt - head) / 4;
+        const int tail0 = head + nvec * 4;
+        {
+            const float4* src = reinterpret_cast<const float4*>(a.pconf + base + head);
+            for (int i = tid; i < nvec; i += RL_THREADS) {
+                const float4 v = src[i];
+                float* d = s_z + head + 4 * i;
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+            if (tid < head) s_z[tid] = a.pconf[base + tid];
+            if (tid < nflt - tail0) s_z[tail0 + tid] = a.pconf[base + tail0 + tid];
+        }
+        __syncthreads();
+        for (int r0 = 0; r0 < TILE; r0 += RW_GROUPS) {      // (compile-time trip count: whole waves reach the shuffles)
+            const int r = r0 + q;
+            const bool on = r < rows;
+            const int an = a0 + (on ? r : 0);
+            const size_t row = (size_t)n * a.A + an;
+            float* z = s_z + (on ? r : 0) * a.C;            // logits in, gradient out (in place: a lane writes the elements it read)
+            const unsigned char st = on ? a.status[row] : 0;
+            const bool focal = st == 1 || st == 2;
+            const int g = st == 1 ? a.rgindex[row] : 0;
+            const int label = st == 1 ? (int)a.gt[((size_t)n * a.P + g) * 5 + 4] : a.C - 1;
+            const float loss = focal_row_wide<K>(a, z, z, label, gs, false, j, focal);
+            if (on && !focal) {                             // ignore band, or a best anchor (its rows are added afterwards)
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if (j + wr::L * k < a.C) z[j + wr::L * k] = 0.f;
+            }
+            if (on && j == 0) {
+                conf += loss;
+                float4 dbv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (st == 1) {
+                    float db[4];
+                    coord += box_row(a, n, an, g, a.pbox + row * 4, db, gs, false);
+                    dbv = make_float4(db[0], db[1], db[2], db[3]);
+                }
+                *reinterpret_cast<float4*>(a.dbox + row * 4) = dbv;
+            }
+        }
+        __syncthreads();
+        {
+            float4* dst = reinterpret_cast<float4*>(a.dconf + base + head);
+            for (int i = tid; i < nvec; i += RL_THREADS) {
+                const float* s = s_z + head + 4 * i;
+                dst[i] = make_float4(s[0], s[1], s[2], s[3]);
+            }
+            if (tid < head) a.dconf[base + tid] = s_z[tid];
+            if (tid < nflt - tail0) a.dconf[base + tail0 + tid] = s_z[tail0 + tid];
+        }
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) { conf += __shfl_xor(conf, o); coord += __shfl_xor(coord, o); }
+    if ((tid & 63) == 0) { s_red[0][tid >> 6] = conf; s_red[1][tid >> 6] = coord; }
+    __syncthreads();
+    if (tid == 0) {
+        float c0 = 0.f, c1 = 0.f;
+        for (int w = 0; w < RL_THREADS / 64; ++w) { c0 += s_red[0][w]; c1 += s_red[1][w]; }
+        float* pp = a.parts + ((size_t)n * gridDim.x + blockIdx.x) * 2;
+        pp[0] = c0 * inv_np;
+        pp[1] = c1 * inv_np;
+    }
+}
+
+// retina_best_rows_kernel for groups: 8 ground-truth rows per pass, the group's first lane carries the sums
+template <int K>
+__global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_wide_kernel(const RLossArgs a, const int nparts) {
+    __shared__ float s_w[2][RL_MAX_GT / 64];
+    const int n = blockIdx.x, tid = threadIdx.x, j = tid & (wr::L - 1), q = tid / wr::L;
+    const int G = a.ngt[n];
+    float conf = 0.f, coord = 0.f;
+    const float inv_np = 1.f / (float)a.counts[n * 4 + 0];
+    const float gs = a.grad_scale * inv_np;
+    for (int g0 = 0; g0 < G; g0 += RL_MAX_GT / wr::L) {
+        const int g = g0 + q;
+        const bool on = g < G;
+        const int an = on ? a.best[(size_t)n * a.P + g] : 0;
+        const size_t row = (size_t)n * a.A + an;
+        const int label = on ? (int)a.gt[((size_t)n * a.P + g) * 5 + 4] : 0;
+        const float loss = focal_row_wide<K>(a, a.pconf + row * a.C, a.dconf + row * a.C, label, gs, true, j, on);
+        if (on && j == 0) {
+            conf += loss;
+            coord += box_row(a, n, an, g, a.pbox + row * 4, a.dbox + row * 4, gs, true);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { conf += __shfl_xor(conf, o); coord += __shfl_xor(coord, o); }
+    if ((tid & 63) == 0) { s_w[0][tid >> 6] = conf * inv_np; s_w[1][tid >> 6] = coord * inv_np; }
+    __syncthreads();
+    if (tid < 2) {                                     // fixed order: the loss pass's workgroups, then this launch's waves
+        float t = 0.f;
+        const float* pp = a.parts + (size_t)n * nparts * 2 + tid;
+        for (int b = 0; b < nparts; ++b) t += pp[2 * b];
+        for (int w = 0; w < RL_MAX_GT / 64; ++w) t += s_w[tid][w];
+        a.loss_parts[n * 2 + tid] = t;
+    }
+}
+
+template <int K>
+static int retina_loss_wide_launch(RLossArgs& a, hipStream_t st) {
+    const int nparts = ceil_div(a.A, RW_ROWS);
+    char* parts = nullptr;
+    if (int e = cv::misc_scratch((size_t)a.N * nparts * 2 * sizeof(float), st, &parts)) return e;
+    a.parts = (float*)parts;
+    hipLaunchKernelGGL(retina_loss_wide_kernel<K>, dim3(nparts, a.N), dim3(RL_THREADS), 0, st, a);
+    hipLaunchKernelGGL(retina_best_rows_wide_kernel<K>, dim3(a.N), dim3(RL_MAX_GT), 0, st, a, nparts);
+    ODTK_LAUNCH_CHECK();
+    return ODTK_OK;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Classification pre-training head (RetinaNet.py:120-135): global average pool of the last residual unit, sparse softmax
@@ -506,16 +669,19 @@ extern "C" int odtk_retina_loss(const float* pconf, const float* pbox, int N, in
                                 float gamma, float grad_scale, float* loss_parts, float* dconf, float* dbox, void* stream) {
     ODTK_REQUIRE(pconf && pbox && yx && hw && gt && ngt && best && status && rgindex && counts && loss_parts && dconf && dbox,
                  "retina_loss: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= RL_MAXC && P > 0 && P <= RL_MAX_GT, "retina_loss: C=%d P=%d unsupported", C, P);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && P > 0 && P <= RL_MAX_GT, "retina_loss: C=%d P=%d unsupported (2 <= C <= %d, P <= %d)", C, P, wr::MAXC, RL_MAX_GT);
     hipStream_t st = (hipStream_t)stream;
-    const int nparts = ceil_div(ceil_div(A, RL_THREADS), RL_LOSS_TILES);
-    char* parts = nullptr;
-    if (int e = cv::misc_scratch((size_t)N * nparts * 2 * sizeof(float), st, &parts)) return e;
     RLossArgs a;
-    a.parts = (float*)parts;
     a.pconf = pconf; a.pbox = pbox; a.N = N; a.A = A; a.C = C; a.yx = yx; a.hw = hw; a.gt = gt; a.P = P;
     a.ngt = ngt; a.best = best; a.status = status; a.rgindex = rgindex; a.counts = counts;
     a.alpha = alpha; a.gamma = gamma; a.grad_scale = grad_scale; a.loss_parts = loss_parts; a.dconf = dconf; a.dbox = dbox;
+    if (C > RL_MAXC) {                                   // 33 .. wr::MAXC logits: a 16-lane group per row
+        ODTK_WIDE_SLOTS(C, K, return retina_loss_wide_launch<K>(a, st));
+    }
+    const int nparts = ceil_div(ceil_div(A, RL_THREADS), RL_LOSS_TILES);
+    char* parts = nullptr;
+    if (int e = cv::misc_scratch((size_t)N * nparts * 2 * sizeof(float), st, &parts)) return e;
+    a.parts = (float*)parts;
     hipLaunchKernelGGL(retina_loss_kernel, dim3(nparts, N), dim3(RL_THREADS), 0, st, a);
     hipLaunchKernelGGL(retina_best_rows_kernel, dim3(N), dim3(RL_MAX_GT), 0, st, a, nparts);
     ODTK_LAUNCH_CHECK();

@@ -77,6 +77,7 @@ HEAD_LAYERS = 11                                               # the last 11 spe
 
 class FCOS(EvaluateMixin, F32Warmup, graph.SharedGradients, DetectorBase):
     def __init__(self, config, data_provider):
+        ops.check_num_classes('FCOS', config['num_classes'], background=False)
         self._prologue(config, data_provider)
         self.data_shape = config['data_shape']
         # engine: bf16 by default on the GPU since round 3 (warmup.py: the first f32_warmup_steps optimizer steps of a run from random initialisation go through

@@ -405,8 +405,23 @@ def nms_batched(boxes, box_stride, scores, score_bstride, score_estride, valid, 
          float(iou_thr), _p(out_idx), cap, _p(out_cnt), _stream())
 
 
+# Logits per row the softmax box-side entry points take (odtk_ssd_loss, odtk_ssd_decode[_batched], odtk_retina_loss, odtk_retina_decode[_batched]: background
+# included, so 255 object classes) and classes odtk_fcos_loss takes (no background column); include/odtk.h, "Class limits".
+MAX_ROW_LOGITS = 256
+MAX_FCOS_CLASSES = 256
+
+
+def check_num_classes(who, num_classes, background):
+    """the constructors' check of config['num_classes'] (object classes) against the limit of the class's box-side kernels"""
+    limit = MAX_ROW_LOGITS - 1 if background else MAX_FCOS_CLASSES
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= limit:
+        raise ValueError(f'{who}: num_classes={num_classes!r} out of range: 1..{limit} object classes'
+                         + (f' ({MAX_ROW_LOGITS} logits per row with the background)' if background else ''))
+
+
 def ssd_loss(pred, Cn, yx, hw, gt, ngt, best, status, rgindex, counts, negloss, sel_idx, sel_cnt, grad_scale,
              loss_parts, dpred):
+    """SSD300.py:430-450 for the batch; pred [N, A, ld] with Cn <= MAX_ROW_LOGITS logits (background last) and 4 regressions per row, ld >= Cn + 4"""
     N, A, ld = pred.shape
     call("odtk_ssd_loss", _p(pred), N, A, Cn, ld, _p(yx), _p(hw), _p(gt), gt.shape[1], _p(ngt), _p(best),
          _p(status), _p(rgindex), _p(counts), _p(negloss), _p(sel_idx), sel_idx.shape[1], _p(sel_cnt),
@@ -414,6 +429,7 @@ def ssd_loss(pred, Cn, yx, hw, gt, ngt, best, status, rgindex, counts, negloss, 
 
 
 def ssd_decode(pred0, Cn, yx, hw, thr, conf, boxes, keep, cand):
+    """SSD300.py:157-171 for one image: pred0 [A, ld], Cn <= MAX_ROW_LOGITS -> conf, cand [A, Cn-1], boxes [A, 4], keep [A]"""
     A, ld = pred0.shape
     call("odtk_ssd_decode", _p(pred0), A, Cn, ld, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep),
          _p(cand), _stream())
@@ -421,13 +437,14 @@ def ssd_decode(pred0, Cn, yx, hw, thr, conf, boxes, keep, cand):
 
 # ------------------------------------------------------------------ batched inference tail (csrc/detect_batched.hip)
 def ssd_decode_batched(pred, Cn, yx, hw, thr, conf, boxes, keep, cand):
-    """odtk_ssd_decode for N images in one launch: pred [N, A, ld] -> conf, cand [N, A, Cn-1], boxes [N, A, 4], keep [N, A]"""
+    """odtk_ssd_decode for N images in one launch: pred [N, A, ld], Cn <= MAX_ROW_LOGITS -> conf, cand [N, A, Cn-1], boxes [N, A, 4], keep [N, A]"""
     N, A, ld = pred.shape
     call("odtk_ssd_decode_batched", _p(pred), N, A, Cn, ld, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep), _p(cand), _stream())
 
 
 def retina_decode_batched(pconf, pbox, yx, hw, thr, conf, boxes, keep, cand):
-    """odtk_retina_decode for N images in one launch: pconf [N, A, C], pbox [N, A, 4] -> conf, cand [N, A, C-1], boxes [N, A, 4], keep [N, A]"""
+    """odtk_retina_decode for N images in one launch: pconf [N, A, C] (C <= MAX_ROW_LOGITS), pbox [N, A, 4] -> conf, cand [N, A, C-1], boxes [N, A, 4],
+    keep [N, A]"""
     N, A, Cn = pconf.shape
     call("odtk_retina_decode_batched", _p(pconf), _p(pbox), N, A, Cn, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes), _p(keep), _p(cand), _stream())
 
@@ -504,6 +521,7 @@ def retina_match(y1x1, y2x2, hw, gt, ngt, best, status, rgindex, counts, ws):
 
 def retina_loss(pconf, pbox, yx, hw, gt, ngt, best, status, rgindex, counts, alpha, gamma, grad_scale, loss_parts,
                 dconf, dbox):
+    """RetinaNet.py:417-474 for the batch; pconf [N, A, C] with C <= MAX_ROW_LOGITS logits per row (background last); loss_parts [N, 2]"""
     N, A, Cn = pconf.shape
     call("odtk_retina_loss", _p(pconf), _p(pbox), N, A, Cn, _p(yx), _p(hw), _p(gt), gt.shape[1], _p(ngt), _p(best),
          _p(status), _p(rgindex), _p(counts), float(alpha), float(gamma), float(grad_scale), _p(loss_parts), _p(dconf),
@@ -533,7 +551,7 @@ def refinedet_decode(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr):
 
 
 def retina_decode(pconf, pbox, yx, hw, thr):
-    """RetinaNet.py:224-238 for one image: pconf [A,C], pbox [A,4] -> conf [A,C-1], boxes [A,4], keep [A], cand [A,C-1]."""
+    """RetinaNet.py:224-238 for one image: pconf [A,C] (C <= MAX_ROW_LOGITS), pbox [A,4] -> conf [A,C-1], boxes [A,4], keep [A], cand [A,C-1]."""
     A, Cn = pconf.shape
     dev = pconf.device
     conf = torch.empty(A, Cn - 1, device=dev)
@@ -600,7 +618,7 @@ def fcos_workspace(conf, N, device):
 
 
 def fcos_loss(conf, reg, center, gt, grad_scale, loss, d_conf, d_reg, d_center, ws):
-    """FCOS.py:153-189 + :266-348.  conf / reg / center: lists of the five level tensors [N,H,W,C|4|1]."""
+    """FCOS.py:153-189 + :266-348.  conf / reg / center: lists of the five level tensors [N,H,W,C|4|1], C <= MAX_FCOS_CLASSES."""
     N, Cn = conf[0].shape[0], conf[0].shape[-1]
     call("odtk_fcos_loss", _ptr_array(conf), _ptr_array(reg), _ptr_array(center), _fcos_shapes(conf), _p(gt), N, Cn,
          gt.shape[1], float(grad_scale), _p(loss), _ptr_array(d_conf), _ptr_array(d_reg), _ptr_array(d_center), _p(ws), _stream())

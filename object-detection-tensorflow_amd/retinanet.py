@@ -89,6 +89,8 @@ class RetinaNet(heads.BatchedInference, graph.SharedGradients, DetectorBase):
         self._prologue(config, data_provider, native_test_batch=True)
         self.block_list = list(config['residual_block_list'])
         self.data_shape = config['data_shape']
+        if not self.is_pretraining:                 # (the pre-training head has its own 224 logits: config['num_classes'] plays no part)
+            ops.check_num_classes('RetinaNet', config['num_classes'], background=True)
         self.num_classes = config['num_classes'] + 1
         self.gamma, self.alpha = config['gamma'], config['alpha']
         self.num_anchors = len(ASPECT_RATIOS) * len(ANCHOR_SCALES)

@@ -175,6 +175,7 @@ class SSD300(BatchedInference, F32Warmup, DetectorBase):
         self.input_size = self.INPUT_SIZE
         self.data_format = config['data_format']
         self.data_shape = [self.INPUT_SIZE, self.INPUT_SIZE, 3] if self.data_format == 'channels_last' else [3, self.INPUT_SIZE, self.INPUT_SIZE]
+        ops.check_num_classes(type(self).__name__, config['num_classes'], background=True)
         self.num_classes = config['num_classes'] + 1          # background = LAST index
         self.weight_decay = config['weight_decay']
         self.prob = 1. - config['keep_prob']                  # unused, as in the reference
