@@ -2,7 +2,8 @@
 """The reference's driver flow (testSSD300.py / testYOLOv3.py: config dict -> data provider -> model -> train_one_epoch ->
 save_weight -> test_one_image) on synthetic VOC-shaped pictures, with the GPU augmentor in front of the model.  After every epoch the model is
 evaluated on a held-out synthetic validation set (VOC07 mAP, model.evaluate(batch_size=...): batched inference) and saved as 'best' when the mAP improves.
-Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet] [epochs] [classes]      (classes: 20 by default; 80 for a COCO-sized head)
+Needs an MI355X:   python examples/train_synthetic.py [ssd300|yolov3|retinanet|refinedet|pfpnet] [epochs] [classes]
+(classes: 20 by default; 80 for a COCO-sized head; up to 255 for every class with a softmax row, refinedet and pfpnet included)
 
 What changes for a user of the reference:
     import SSD300 as net; model = net.SSD300(config, data_provider)        ->   from odtk import SSD300
@@ -22,7 +23,7 @@ from odtk.augment import Augmentor            # noqa: E402
 which = sys.argv[1] if len(sys.argv) > 1 else 'ssd300'
 epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 num_classes = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-size = {'ssd300': 300, 'yolov3': 416, 'retinanet': 512}[which]
+size = {'ssd300': 300, 'yolov3': 416, 'retinanet': 512, 'refinedet': 320, 'pfpnet': 320}[which]
 batch_size = 8
 dev = torch.device('cuda:0')
 
@@ -64,6 +65,11 @@ elif which == 'retinanet':
               'batch_size': batch_size, 'gamma': 2.0, 'alpha': 0.25, 'nms_score_threshold': 0.8, 'nms_max_boxes': 10,
               'nms_iou_threshold': 0.45}                                                                # testretinanet.py:22-41
     model = odtk.RetinaNet(config, data_provider)
+elif which in ('refinedet', 'pfpnet'):
+    config = {'mode': 'train', 'input_size': size, 'data_format': 'channels_last', 'num_classes': num_classes, 'weight_decay': 1e-4, 'keep_prob': 0.5,
+              'batch_size': batch_size, 'nms_score_threshold': 0.1, 'nms_max_boxes': 20, 'nms_iou_threshold': 0.45,
+              'pretraining_weight': './vgg_16.ckpt'}                                                    # testrefinedet.py:15-33
+    model = (odtk.RefineDet320 if which == 'refinedet' else odtk.PFPNetR)(config, data_provider)
 else:
     config = {'mode': 'train', 'data_shape': [size, size, 3], 'num_classes': num_classes, 'weight_decay': 5e-4, 'keep_prob': 0.5, 'data_format': 'channels_last',
               'batch_size': batch_size, 'coord_scale': 1, 'noobj_scale': 1, 'obj_scale': 5., 'class_scale': 1., 'num_priors': 3,

@@ -471,6 +471,16 @@ int odtk_detection_pack(const int* nms_idx, const int* nms_cnt, int N, int num_c
  *     - every output is bit-identical from run to run wherever it is below the limit: all but the elements of rows added to three times or more.
  *   FCOS, C > 64: the thread-per-location layout with four 64-bit words of heat-map target instead of one; the classes of a location are added in ascending
  *   order on both sides of the limit, no atomics: bit-identical from run to run.
+ * odtk_refinedet_loss, odtk_refinedet_decode and odtk_refinedet_decode_batched (RefineDet320 / PFPNetR) take ODM rows of 2 <= C <= 256 logits, the background
+ * included (255 object classes), since version 108; more is refused in the same way.  Their one-thread kernels reach further than those above:
+ *   C <= 96: one thread per row, the classes added in order: every output has the bits of the versions before 108.
+ *   C  > 96: a group of 16 adjacent lanes per row with 8 (C <= 128) or 16 registers per lane; maximum, sum of exponentials (lane j's classes in ascending
+ *     order, then the butterfly over 8, 4, 2, 1) and arg-max (ties to the lower class index) as stated above.  What does not read the ODM logits -- the
+ *     two-logit ARM softmax and its `< 0.99` tests, the box arithmetic of both stages, the smooth-L1 terms -- is evaluated per row by the statements of the
+ *     one-thread kernels: boxes do not depend on C.  The loss adds a row's ODM gradient into the zeroed d_odm_conf with float atomics, one class per lane, as the
+ *     one-thread kernel does per thread (a row that is the best anchor of two boxes, or of one and a positive besides, is added to more than once);
+ *     the per-image sums are taken over the rows of every 16th group instead of every 256th thread, then by the same workgroup and split reduction:
+ *     loss_parts is bit-identical from run to run, the gradients wherever a row is added to at most twice.
  *
  * SSD300._compute_one_image_loss steps 8-12 (SSD300.py:427-453) + the batch mean
  * (SSD300.py:148) and its gradient.  loss_parts[N][4] = {neg, pos_conf, coord, total};
@@ -515,7 +525,8 @@ int odtk_retina_match(const float* y1x1, const float* y2x2, const float* hw, int
  * ARM: mean CE of the mined negatives, mean CE + smooth-L1 of the positive rows against the anchors.  ODM: mean CE against background of the mined
  * negatives whose ARM background LOGIT is < 0.99 (sic), mean CE + smooth-L1 of the positive rows against the ARM-REFINED anchors -- the box term
  * also differentiates the refined anchors (no stop_gradient in the reference).  loss_parts [N][8] = {arm negatives, arm positives, arm boxes,
- * odm negatives, odm positives, odm boxes, total, #odm negatives}; the four gradients (of sum_n total_n * grad_scale) are fully written. */
+ * odm negatives, odm positives, odm boxes, total, #odm negatives}; the four gradients (of sum_n total_n * grad_scale) are fully written.
+ * 2 <= C <= 256 ("Class limits" above: C > 96 runs a 16-lane group per ODM row); means of empty sets are NaN (0 / 0) on both sides of 96. */
 int odtk_refinedet_loss(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, int N, int A, int C,
                         const float* yx, const float* hw, const float* gt, int P, const int* ngt, const int* best,
                         const unsigned char* status, const int* rgindex, const int* counts, const float* negloss, const int* sel_idx,
@@ -523,7 +534,8 @@ int odtk_refinedet_loss(const float* arm_loc, const float* arm_conf, const float
                         float* d_odm_loc, float* d_odm_conf, void* stream);
 /* RefineDet inference decode (RefineDet.py:189-206) for one image: keep[a] = softmax(arm)[1] < 0.99 and arg-max(softmax(odm)) != background;
  * conf [A][C-1] = softmax(odm) without the background column; boxes [A][4] y1x1y2x2 decoded through both stages; cand = keep and conf >= threshold
- * (the per-class NMS that follows is odtk_nms_batched, as for SSD300). */
+ * (the per-class NMS that follows is odtk_nms_batched, as for SSD300).  2 <= C <= 256; the arg-max is taken over the probabilities, first maximum
+ * ("Class limits" above: C > 96 runs a 16-lane group per anchor; conf then carries the butterfly sum, boxes the bits of the one-thread kernel). */
 int odtk_refinedet_decode(const float* arm_loc, const float* arm_conf, const float* odm_loc, const float* odm_conf, int A, int C,
                           const float* yx, const float* hw, float score_threshold, float* conf, float* boxes, unsigned char* keep,
                           unsigned char* cand, void* stream);

@@ -405,8 +405,8 @@ def nms_batched(boxes, box_stride, scores, score_bstride, score_estride, valid, 
          float(iou_thr), _p(out_idx), cap, _p(out_cnt), _stream())
 
 
-# Logits per row the softmax box-side entry points take (odtk_ssd_loss, odtk_ssd_decode[_batched], odtk_retina_loss, odtk_retina_decode[_batched]: background
-# included, so 255 object classes) and classes odtk_fcos_loss takes (no background column); include/odtk.h, "Class limits".
+# Logits per row the softmax box-side entry points take (odtk_ssd_loss, odtk_ssd_decode[_batched], odtk_retina_loss, odtk_retina_decode[_batched],
+# odtk_refinedet_loss, odtk_refinedet_decode[_batched]: background included, so 255 object classes) and classes odtk_fcos_loss takes (no background column); include/odtk.h, "Class limits".
 MAX_ROW_LOGITS = 256
 MAX_FCOS_CLASSES = 256
 
@@ -450,8 +450,8 @@ def retina_decode_batched(pconf, pbox, yx, hw, thr, conf, boxes, keep, cand):
 
 
 def refinedet_decode_batched(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr, conf, boxes, keep, cand):
-    """odtk_refinedet_decode for N images in one launch: arm_loc / odm_loc [N, A, 4], arm_conf [N, A, 2], odm_conf [N, A, C] -> conf, cand [N, A, C-1],
-    boxes [N, A, 4], keep [N, A]"""
+    """odtk_refinedet_decode for N images in one launch: arm_loc / odm_loc [N, A, 4], arm_conf [N, A, 2], odm_conf [N, A, C] (C <= MAX_ROW_LOGITS)
+    -> conf, cand [N, A, C-1], boxes [N, A, 4], keep [N, A]"""
     N, A, Cn = odm_conf.shape
     call("odtk_refinedet_decode_batched", _p(arm_loc), _p(arm_conf), _p(odm_loc), _p(odm_conf), N, A, Cn, _p(yx), _p(hw), float(thr), _p(conf), _p(boxes),
          _p(keep), _p(cand), _stream())
@@ -530,7 +530,8 @@ def retina_loss(pconf, pbox, yx, hw, gt, ngt, best, status, rgindex, counts, alp
 
 def refinedet_loss(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, gt, ngt, best, status, rgindex, counts, negloss, sel_idx, sel_cnt, grad_scale,
                    loss_parts, d_arm_loc, d_arm_conf, d_odm_loc, d_odm_conf):
-    """RefineDet.py:422-567 for the batch (include/odtk.h: odtk_refinedet_loss); loss_parts [N, 8]"""
+    """RefineDet.py:422-567 for the batch (include/odtk.h: odtk_refinedet_loss); odm_conf [N, A, C] with C <= MAX_ROW_LOGITS logits per row (background
+    last; above 96 a 16-lane group per row); loss_parts [N, 8]"""
     N, A, Cn = odm_conf.shape
     call("odtk_refinedet_loss", _p(arm_loc), _p(arm_conf), _p(odm_loc), _p(odm_conf), N, A, Cn, _p(yx), _p(hw), _p(gt), gt.shape[1], _p(ngt),
          _p(best), _p(status), _p(rgindex), _p(counts), _p(negloss), _p(sel_idx), sel_idx.shape[1], _p(sel_cnt), float(grad_scale), _p(loss_parts),
@@ -538,7 +539,7 @@ def refinedet_loss(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, gt, ngt, best, 
 
 
 def refinedet_decode(arm_loc, arm_conf, odm_loc, odm_conf, yx, hw, thr):
-    """RefineDet.py:189-206 for one image -> conf [A, C-1], boxes [A, 4], keep [A], cand [A, C-1]"""
+    """RefineDet.py:189-206 for one image: odm_conf [A, C] (C <= MAX_ROW_LOGITS) -> conf [A, C-1], boxes [A, 4], keep [A], cand [A, C-1]"""
     A, Cn = odm_conf.shape
     dev = odm_conf.device
     conf = torch.empty(A, Cn - 1, device=dev)

@@ -80,6 +80,9 @@ class RefineDet320(heads.BatchedInference, F32Warmup, graph.OwnedGradients, Dete
         return layer_specs(num_classes)
 
     def __init__(self, config, data_provider):
+        # config['num_classes'] counts the object classes (RefineDet.py:41); the ODM row has one more logit, the background (pfpnet.PFPNetR comes through
+        # here; yolov2.YOLOv2 has a constructor of its own and no row kernel)
+        ops.check_num_classes(self.NAME, config['num_classes'], background=True)
         self._prologue(config, data_provider, native_test_batch=True)
         self.input_size = config['input_size']
         self.data_shape = [self.input_size, self.input_size, 3] if config['data_format'] == 'channels_last' else [3, self.input_size, self.input_size]
