@@ -676,7 +676,11 @@ int odtk_depthwise_wgrad(const void* x, int ldx, const void* dy, int lddy, float
  * order -- the G best anchors in box order (duplicates kept), then the status-1 anchors in anchor order -- as pos_anchor / pos_gt / pos_label / pos_score
  * (softmax of the two RPN outputs, column 0) / pos_box (y1,x1,y2,x2 of the anchor) / pos_valid; the NEGATIVE list (status 2, anchor order) with its
  * cross entropy against label 1 as score.  Label of a best row = label[anchor index] if that index < G else 0: tf.gather with the GPU kernel's
- * out-of-range rule (:337).  cap >= A + P is the lists' row pitch.  Feed both lists to odtk_nms_batched (IoU 0.7, max_out = counts[3] / counts[4]). */
+ * out-of-range rule (:337).  cap >= A + P is the lists' row pitch.  Feed both lists to odtk_nms_batched (IoU 0.7, max_out = counts[3] / counts[4]).
+ * A box none of whose IoUs compares greater than another (all NaN: a row of NaN area such as h = inf, w = 0) takes anchor 0 as its best anchor, as the
+ * reference's arg-max does; the search used to keep its start value 0x7fffffff for such a row and wrote status[] and read the anchors ~2 GiB past them.
+ * In the other anchors' maximum over the boxes a NaN IoU is the maximum (as in the oracle's reduction): such an anchor is neither positive nor negative
+ * (status 0); before, the NaN was skipped.  P <= 128, refused otherwise. */
 int odtk_lhrcnn_match(const float* y1x1, const float* y2x2, const float* yx, const float* hw, const int* anchor_row, int A, int A_full,
                       const float* conf, const float* gt, int N, int P, int cap, int* counts, unsigned char* status, int* pos_anchor, int* pos_gt,
                       int* pos_label, float* pos_score, float* pos_box, unsigned char* pos_valid, int* neg_anchor, float* neg_score, float* neg_box,

@@ -237,10 +237,12 @@ __global__ void __launch_bounds__(LH_THREADS) lh_match_kernel(const LhMatchArgs 
     unsigned char* status = a.status + (size_t)n * A;
     for (int i = tid; i < A; i += LH_THREADS) status[i] = 0;
     __syncthreads();
-    // best anchor of every box: first maximum over the anchors (tf.argmax)
+    // best anchor of every box: first maximum over the anchors (tf.argmax).  A thread without an anchor, or one whose IoUs are all NaN (a box of NaN
+    // area: h = inf, w = 0), keeps (-1, 0): any real IoU (>= 0) beats it, and a box with no comparable IoU at all gets anchor 0, as the arg-max of the
+    // reference does -- never an index outside [0, A)
     for (int g = 0; g < G; ++g) {
         float bv = -1.f;
-        int bi = 0x7fffffff;
+        int bi = 0;
         for (int i = tid; i < A; i += LH_THREADS) {
             const float v = lh_iou(a.an.y1x1 + 2 * i, a.an.y2x2 + 2 * i, a.an.hw + 2 * i, s_g[g][0], s_g[g][1], s_g[g][2], s_g[g][3], s_g[g][4]);
             if (v > bv) { bv = v; bi = i; }       // ascending i per thread: a later equal value does not replace
@@ -294,7 +296,7 @@ __global__ void __launch_bounds__(LH_THREADS) lh_match_kernel(const LhMatchArgs 
             float mv = -1.f;
             for (int g = 0; g < G; ++g) {
                 const float v = lh_iou(a.an.y1x1 + 2 * i, a.an.y2x2 + 2 * i, a.an.hw + 2 * i, s_g[g][0], s_g[g][1], s_g[g][2], s_g[g][3], s_g[g][4]);
-                if (v > mv) { mv = v; arg = g; }
+                if (v > mv || (v != v && mv == mv)) { mv = v; arg = g; }       // a NaN IoU (a box of NaN area) is the maximum and stays it, as in the oracle's max
             }
             kind = mv > 0.5f ? 1 : (mv < 0.3f ? 2 : 0);
             status[i] = (unsigned char)kind;
@@ -679,7 +681,8 @@ extern "C" int odtk_lhrcnn_match(const float* y1x1, const float* y2x2, const flo
                                  unsigned char* neg_valid, void* stream) {
     ODTK_REQUIRE(y1x1 && y2x2 && yx && hw && anchor_row && conf && gt && counts && status && pos_anchor && pos_gt && pos_label && pos_score && pos_box && pos_valid &&
                  neg_anchor && neg_score && neg_box && neg_valid, "lhrcnn_match: null pointer");
-    ODTK_REQUIRE(A > 0 && A <= A_full && N > 0 && P > 0 && P <= LH_MAX_GT && cap >= A + P, "lhrcnn_match: A=%d A_full=%d N=%d P=%d cap=%d out of range", A, A_full, N, P, cap);
+    ODTK_REQUIRE(P <= LH_MAX_GT, "lhrcnn_match: P=%d ground-truth rows per image, at most %d are staged", P, LH_MAX_GT);
+    ODTK_REQUIRE(A > 0 && A <= A_full && N > 0 && P > 0 && cap >= A + P, "lhrcnn_match: A=%d A_full=%d N=%d P=%d cap=%d out of range", A, A_full, N, P, cap);
     LhMatchArgs a;
     a.an = lh_anchors(y1x1, y2x2, yx, hw, anchor_row, A, A_full);
     a.conf = conf; a.gt = gt; a.P = P; a.cap = cap; a.counts = counts; a.status = status;
@@ -697,7 +700,8 @@ extern "C" int odtk_lhrcnn_rpn_loss(const float* y1x1, const float* y2x2, const 
                                     float* roi_prop, float* roi_truth, int* roi_img, int* roi_label, int* roi_kind, int* roi_counts, void* stream) {
     ODTK_REQUIRE(yx && hw && anchor_row && conf && bbox && gt && pos_anchor && pos_gt && pos_label && neg_anchor && sel_pos && cnt_pos && sel_neg && cnt_neg &&
                  loss_parts && d_conf && d_bbox && roi_box && roi_prop && roi_truth && roi_img && roi_label && roi_kind && roi_counts, "lhrcnn_rpn_loss: null pointer");
-    ODTK_REQUIRE(A > 0 && A <= A_full && N > 0 && P > 0 && P <= LH_MAX_GT && num_classes > 1 && img_h > 1 && img_w > 1, "lhrcnn_rpn_loss: argument out of range");
+    ODTK_REQUIRE(P <= LH_MAX_GT, "lhrcnn_rpn_loss: P=%d ground-truth rows per image, at most %d (the limit of odtk_lhrcnn_match)", P, LH_MAX_GT);
+    ODTK_REQUIRE(A > 0 && A <= A_full && N > 0 && P > 0 && num_classes > 1 && img_h > 1 && img_w > 1, "lhrcnn_rpn_loss: argument out of range");
     hipStream_t st = (hipStream_t)stream;
     if (int e = zero_async(d_conf, (size_t)N * A_full * 2 * sizeof(float), st)) return e;
     if (int e = zero_async(d_bbox, (size_t)N * A_full * 4 * sizeof(float), st)) return e;
