@@ -198,7 +198,8 @@ int odtk_avgpool2x2_bwd(const void* dy, void* dx, int N, int H, int W, int ld, i
 int odtk_add_relu_fwd(const void* a, int lda, const void* b, int ldb, void* y, int ldy, long long M, int C, int dtype, void* stream);
 int odtk_relu_bwd(const void* y, const void* dy, int ldy, void* dx, int lddx, long long M, int C, int dtype, int accumulate, void* stream);
 
-/* tf.layers.max_pooling2d SAME (SSD300.py:539-547): kxk window, stride, pad_before. */
+/* tf.layers.max_pooling2d SAME (SSD300.py:539-547): kxk window, stride, pad_before.  All pooling entry points below work on the C columns of a row:
+ * pad columns [C, ld) of x and dy are not read, those of y and dx keep what they held. */
 int odtk_maxpool_fwd(const void* x, void* y, int N, int H, int W, int C, int ld, int Ho, int Wo,
                      int k, int stride, int pad_t, int pad_l, int dtype, void* stream);
 /* gradient routed to the FIRST maximum of each window (row-major scan), summed over
@@ -321,7 +322,8 @@ int odtk_rows_to_f32(const void* x, int ldx, int dtype, float* y, int ldy, int r
 int odtk_rows_from_f32(const float* y, int ldy, int rows_per_img, long long y_img_stride, void* x, int ldx, int dtype, long long M, int C,
                        void* stream);
 
-/* tf.nn.l2_normalize(axis=C) * scalar gamma (SSD300.py:74-83). */
+/* tf.nn.l2_normalize(axis=C) * scalar gamma (SSD300.py:74-83).  Forward and backward work on the C columns of a row: pad columns [C, ld) of the
+ * inputs are not read, those of y and dx keep what they held. */
 int odtk_l2norm_fwd(const void* x, void* y, int M, int C, int ld, int dtype, const float* gamma,
                     void* stream);
 /* dx += (accumulate) ; dgamma[0] += sum (caller zeroes). relu_src masks like dgrad.
@@ -331,7 +333,8 @@ int odtk_l2norm_bwd(const void* x, const void* dy, void* dx, int M, int C, int l
                     const float* gamma, float* dgamma, int accumulate, const void* relu_src,
                     void* stream);
 
-/* column sums: out[c] (+)= sum_m dy[m][c]  (bias gradient), f32 out. */
+/* column sums: out[c] (+)= sum_m dy[m][c]  (bias gradient), f32 out.  Pad columns [C, ld) of dy are loaded with the last chunk and never stored; the
+ * workspace (odtk_bn_workspace_bytes) receives whole rows of C partial sums from its start and nothing else. */
 int odtk_colsum(const void* dy, int M, int C, int ld, int dtype, float* out, int accumulate,
                 void* workspace, void* stream);
 
