@@ -379,7 +379,7 @@ int odtk_ssd_priors(int input_size, int nlevels, const int* fsize /*host*/, cons
                     float* nmsbox, void* stream);
 
 /* SSD300._compute_one_image_loss steps 1-7 (SSD300.py:347-426), one workgroup per image.
- * gt [N][P][5] = (yc, xc, h, w, cls), padded rows -1.  Outputs:
+ * gt [N][P][5] = (yc, xc, h, w, cls), padded rows -1, P <= 1024 ("Ground-truth rows" below).  Outputs:
  *  ngt[N]; best[N][P] (anchor id per GT, first max); status[N][A] u8: 0 = best anchor of some
  *  GT, 1 = positive (max IoU > 0.5), 2 = negative; rgindex[N][A] (arg-max GT, first max);
  *  counts[N][4] = {num_pos (= ngt + #status1), num_neg, chosen_num_neg, 0}. */
@@ -458,6 +458,16 @@ int odtk_detection_pack(const int* nms_idx, const int* nms_cnt, int N, int num_c
                         const float* boxes, long long box_istride, int* counts, int* offsets, float* scores, float* bbox, int* class_id,
                         void* stream);
 
+/* ---- Ground-truth rows ----
+ * Every matching and loss entry point takes the ground truth as gt [N][P][5] (P = the generator's pad_truth_to; the rows in front of the first minimum of
+ * column 0 are the boxes) and stages an image's boxes in LDS.  odtk_ssd_match, odtk_retina_match (also in front of odtk_refinedet_loss), odtk_retina_loss,
+ * odtk_fcos_loss, odtk_centernet_loss and odtk_yolov3_loss take 1 <= P <= 1024; odtk_yolov2_loss, odtk_lhrcnn_match and odtk_lhrcnn_rpn_loss 1 <= P <= 128.
+ * More is refused with ODTK_ERR_ARG and a message naming P and the limit, before any launch.  The kernels that stage boxes are compiled for a capacity of
+ * 128 and of 1024 rows and the host picks by P: P <= 128 runs the kernel, LDS footprint, launch shape and arithmetic it always ran (results bit for bit),
+ * P > 128 the same code with the larger arrays (at most 56 KiB of LDS per workgroup).  odtk_ssd_loss and odtk_refinedet_loss index best [N][P] by box
+ * number < ngt[n] <= P only and have no limit of their own.  The tie rules (first minimum for the count, first maximum over boxes and over anchors,
+ * duplicates allowed in best) are those of the reference at every P. */
+
 /* ---- Class limits of the softmax box side, and the numerics on either side of them ----
  * odtk_ssd_loss, odtk_ssd_decode, odtk_ssd_decode_batched, odtk_retina_loss, odtk_retina_decode and odtk_retina_decode_batched take rows of 2 <= C <= 256
  * logits, the background included (255 object classes); odtk_fcos_loss takes 1 <= C <= 256 classes (no background column).  More is refused with
@@ -504,7 +514,7 @@ int odtk_ssd_decode(const float* pred0, int A, int C, int ld, const float* yx, c
 /* ------------------------------------------------------------------------- *
  * RetinaNet box side (kernel K16): anchors, matching with the 0.4 / 0.5 ignore band,
  * softmax focal loss + smooth-L1 and their gradients.  Any number of anchors (47 961 @500x500,
- * 120 087 @800x800); same GT layout as SSD ([N][P][5] = yc, xc, h, w, class; pad rows -1; P <= 128).
+ * 120 087 @800x800); same GT layout as SSD ([N][P][5] = yc, xc, h, w, class; pad rows -1; P <= 1024, "Ground-truth rows" above).
  * ------------------------------------------------------------------------- */
 /* RetinaNet._get_abbox (RetinaNet.py:328-355) for every pyramid level: level l has fh[l] x fw[l] cells and
  * na[l] anchors per cell whose (h, w) follow in prior_hw (host floats, level-major); centre = (i + 0.5) *
@@ -546,7 +556,7 @@ int odtk_refinedet_decode(const float* arm_loc, const float* arm_conf, const flo
 /* Focal (softmax flavour, alpha on positives AND negatives, p clipped to [1e-8, 1], sum / #positives;
  * RetinaNet.py:457-474) + smooth-L1 on the positive rows (:441-446).  pconf [N][A][C] logits (background =
  * class C-1), pbox [N][A][4] = (ty, tx, th, tw).  loss_parts[N][2] = {focal, coord}; dconf / dbox are
- * overwritten with d(sum_i (focal_i + coord_i) * grad_scale) / d(pconf, pbox)  (grad_scale = 1 / batch).  2 <= C <= 256, P <= 128.  C > 32 ("Class
+ * overwritten with d(sum_i (focal_i + coord_i) * grad_scale) / d(pconf, pbox)  (grad_scale = 1 / batch).  2 <= C <= 256, P <= 1024.  C > 32 ("Class
  * limits" above): a 16-lane group per row, rows staged through 32 KiB of LDS in tiles of 128 / 64 / 32 rows for C <= 64 / 128 / 256; the loss is the sum
  * of one partial per 512 rows in row order, then the best-anchor rows. */
 int odtk_retina_loss(const float* pconf, const float* pbox, int N, int A, int C, const float* yx,
@@ -576,7 +586,7 @@ int odtk_retina_decode(const float* pconf, const float* pbox, int A, int C, cons
  * _gaussian_radius (CenterNet.py:187-270) + the batch mean (:144-152) and the inference branch (:159-185).
  * keypoints [N][H][W][C] logits, offset / size [N][H][W][2], gt [N][P][5] = yc,xc,h,w,cls px (pad rows -1).
  * loss_parts [N][4] = keypoint, offset, size, total per image; d_* = grad_scale * d(sum_n total_n)/d(input)
- * (pass grad_scale = 1/N for the reference's batch mean).  workspace: odtk_centernet_workspace_bytes. */
+ * (pass grad_scale = 1/N for the reference's batch mean).  workspace: odtk_centernet_workspace_bytes.  P <= 1024 ("Ground-truth rows" above). */
 long long odtk_centernet_workspace_bytes(int N, int H, int W, int C);
 int odtk_centernet_loss(const float* keypoints, const float* offset, const float* size, const float* gt, int N, int H,
                         int W, int C, int P, float stride, float grad_scale, float* loss_parts, float* d_keypoints,
@@ -592,7 +602,7 @@ int odtk_centernet_decode(const float* keypoints, const float* offset, const flo
  * (FCOS.py:153-189, :266-348) and the decode candidates (FCOS.py:197-246; feed them to odtk_nms_batched).
  * conf / reg / center: host arrays of 5 device pointers (p3..p7) to [N][H_l][W_l][C] logits, [..][4] = l,r,t,b
  * distances (> 0, i.e. after the exp), [..][1] centre-ness logits; shapes [5][2] = H_l, W_l; strides 8..128.
- * loss [N] per image; d_* as for CenterNet.  workspace: odtk_fcos_workspace_bytes.  odtk_fcos_loss: 1 <= C <= 256, P <= 128 ("Class limits" above: the
+ * loss [N] per image; d_* as for CenterNet.  workspace: odtk_fcos_workspace_bytes.  odtk_fcos_loss: 1 <= C <= 256, P <= 1024 ("Class limits" above: the
  * results for C <= 64 are those of the one-word kernel, unchanged). */
 long long odtk_fcos_workspace_bytes(const int* shapes, int N);
 int odtk_fcos_loss(const float* const* conf, const float* const* reg, const float* const* center, const int* shapes,
@@ -607,7 +617,7 @@ int odtk_fcos_decode_candidates(const float* const* conf, const float* const* re
  * coarsest) to [N][H_l][W_l][num_priors][C+5] = class(C), yx(2), hw(2), obj(1) logits; shapes [3][2];
  * priors [3][num_priors][2] (h, w) in the units the reference pairs with each head (config priors[i] / stride[i]);
  * head_stride [3] = 32, 16, 8 (ground truth / head_stride); decode_scale [3] = 32, 32, 16 (sic, YOLOv3.py:343-348).
- * loss_parts [N][5] = coord, class, obj, no-object sums and the per-image total; d_pred as for CenterNet. */
+ * loss_parts [N][5] = coord, class, obj, no-object sums and the per-image total; d_pred as for CenterNet.  gt [N][pad][5], pad <= 1024. */
 long long odtk_yolov3_workspace_bytes(const int* shapes, int num_priors, int N);
 int odtk_yolov3_loss(const float* const* pred, const int* shapes, const float* priors, const float* head_stride,
                      const float* gt, int N, int num_priors, int C, int pad, float coord_scale, float noobj_scale,
@@ -619,7 +629,7 @@ int odtk_yolov3_decode_candidates(const float* const* pred, const int* shapes, c
 
 /* YOLOv2 box side: the per-image loss loop of YOLOv2.py:102-166 (batch mean :167) and the decode of :177-186 (feed the candidates to
  * odtk_nms_batched).  pred [N][H][W][num_priors][C+5] = class(C), yx(2), hw(2), obj(1) logits (f32, device); priors: HOST array [num_priors][2] (h, w) in
- * cell units as the reference's config gives them; stride 32 (ground truth pixels / stride); gt [N][pad][5] = yc, xc, h, w, class padded with -1, pad <= 128.
+ * cell units as the reference's config gives them; stride 32 (ground truth pixels / stride); gt [N][pad][5] = yc, xc, h, w, class padded with -1, pad <= 128 (this entry point keeps the narrow limit: "Ground-truth rows" above).
  * loss_parts [N][5] = coord (yx + hw), class, objectness, no-object sums and the scaled per-image total; d_pred (fully written) = d(sum_i total_i) *
  * grad_scale.  The reference's quirks (unclamped intersections, the mangled prior box of the no-object IoU, additive decode) are reproduced. */
 int odtk_yolov2_loss(const float* pred, int N, int H, int W, int num_priors, int C, const float* priors, float stride, const float* gt,
@@ -683,7 +693,7 @@ int odtk_depthwise_wgrad(const void* x, int ldx, const void* dy, int lddy, float
  * A box none of whose IoUs compares greater than another (all NaN: a row of NaN area such as h = inf, w = 0) takes anchor 0 as its best anchor, as the
  * reference's arg-max does; the search used to keep its start value 0x7fffffff for such a row and wrote status[] and read the anchors ~2 GiB past them.
  * In the other anchors' maximum over the boxes a NaN IoU is the maximum (as in the oracle's reduction): such an anchor is neither positive nor negative
- * (status 0); before, the NaN was skipped.  P <= 128, refused otherwise. */
+ * (status 0); before, the NaN was skipped.  P <= 128, refused otherwise (the Light-Head R-CNN entry points keep the narrow limit: "Ground-truth rows" above). */
 int odtk_lhrcnn_match(const float* y1x1, const float* y2x2, const float* yx, const float* hw, const int* anchor_row, int A, int A_full,
                       const float* conf, const float* gt, int N, int P, int cap, int* counts, unsigned char* status, int* pos_anchor, int* pos_gt,
                       int* pos_label, float* pos_score, float* pos_box, unsigned char* pos_valid, int* neg_anchor, float* neg_score, float* neg_box,

@@ -67,6 +67,7 @@ class DetectorBase:
     TF_STATS_OPTIONAL = False         # restore: a moving statistic absent from the file is skipped (RetinaNet: a pre-training file holds none)
     PROGRESS_FROM = 0                 # train_one_epoch prints the iteration counted from here: each reference file's own print
     sinfo = {}                        # a class without moving statistics (FCOS) leaves it empty and has no S
+    GT_ROWS_LIMIT = ops.GT_ROWS_MAX   # ground-truth rows per image (pad_truth_to) the class's matching / loss kernels take (YOLOv2, LHRCNN: GT_ROWS_MAX_NARROW)
     use_graph = False                 # the step's forward + loss + backward replay from one HIP graph (a class reads it from its config)
     _graph, _graph_gt, _eager_steps = None, None, 0
 
@@ -207,6 +208,7 @@ class DetectorBase:
         self.images.copy_(images, non_blocking=True)
         gt = torch.as_tensor(ground_truth, dtype=torch.float32)
         if self.gt is None or self.gt.shape != gt.shape:
+            ops.check_gt_rows(type(self).__name__, gt.shape, self.GT_ROWS_LIMIT)
             self.gt = torch.zeros(gt.shape, device=self.dev)
             self._gt_reshaped(gt.shape)
         self.gt.copy_(gt, non_blocking=True)

@@ -54,7 +54,8 @@ __global__ void priors_kernel(const PriorArgs p, float* __restrict__ y1x1, float
 
 // ------------------------------------------------------------------ matching
 constexpr int MATCH_THREADS = 1024;
-constexpr int MAX_GT = 128;
+constexpr int MAX_GT = 128;                    // ground-truth rows per image of the default instantiation (its LDS footprint is the one every P <= 128 ran with)
+constexpr int MAX_GT_WIDE = 1024;              // ... of the wide one: one row per thread of the workgroup (`tid < G` below); 32 + 20 + 4 KiB of LDS
 constexpr int MAX_ANCH = 32768;                // SSD512 has 24 912 priors (SSD512.py:116-133)
 
 struct GtBox { float y1, x1, y2, x2, area; };
@@ -75,12 +76,14 @@ __device__ __forceinline__ void argmin_combine(float& v, int& i, float v2, int i
     if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
 }
 
+template <int CAP>                             // CAP >= P: the staged boxes (host dispatch in odtk_ssd_match)
 __global__ void __launch_bounds__(MATCH_THREADS) ssd_match_kernel(
     const float* __restrict__ y1x1, const float* __restrict__ y2x2, const float* __restrict__ hw, int A,
     const float* __restrict__ gt, int P, int* __restrict__ ngt, int* __restrict__ best,
     unsigned char* __restrict__ status, int* __restrict__ rgindex, int* __restrict__ counts) {
-    __shared__ GtBox s_g[MAX_GT];
-    __shared__ int s_best[MAX_GT];
+    static_assert(CAP <= MATCH_THREADS, "one thread stages one box");
+    __shared__ GtBox s_g[CAP];
+    __shared__ int s_best[CAP];
     __shared__ unsigned char s_isbest[MAX_ANCH];
     __shared__ float s_rv[MATCH_THREADS / 64];
     __shared__ int s_ri[MATCH_THREADS / 64];
@@ -1118,10 +1121,14 @@ extern "C" int odtk_ssd_match(const float* y1x1, const float* y2x2, const float*
                               int* counts, void* stream) {
     ODTK_REQUIRE(y1x1 && y2x2 && hw && gt && ngt && best && status && rgindex && counts, "ssd_match: null pointer");
     ODTK_REQUIRE(A > 0 && A <= MAX_ANCH, "ssd_match: A=%d out of range (max %d)", A, MAX_ANCH);
-    ODTK_REQUIRE(P > 0 && P <= MAX_GT, "ssd_match: P=%d out of range (max %d)", P, MAX_GT);
+    ODTK_REQUIRE(P > 0 && P <= MAX_GT_WIDE, "ssd_match: P=%d out of range (max %d)", P, MAX_GT_WIDE);
     ODTK_REQUIRE(N > 0, "ssd_match: N must be positive");
-    hipLaunchKernelGGL(ssd_match_kernel, dim3(N), dim3(MATCH_THREADS), 0, (hipStream_t)stream, y1x1, y2x2, hw, A, gt, P,
-                       ngt, best, status, rgindex, counts);
+    if (P <= MAX_GT)
+        hipLaunchKernelGGL(ssd_match_kernel<MAX_GT>, dim3(N), dim3(MATCH_THREADS), 0, (hipStream_t)stream, y1x1, y2x2, hw, A, gt, P,
+                           ngt, best, status, rgindex, counts);
+    else
+        hipLaunchKernelGGL(ssd_match_kernel<MAX_GT_WIDE>, dim3(N), dim3(MATCH_THREADS), 0, (hipStream_t)stream, y1x1, y2x2, hw, A, gt, P,
+                           ngt, best, status, rgindex, counts);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }

@@ -14,6 +14,10 @@ namespace odtk {
 namespace {
 
 constexpr int DH_THREADS = 256, DH_MAX_GT = 128, DH_MAXC = 64;
+// Ground-truth rows per image.  The CenterNet, FCOS and YOLOv3 loss kernels stage the boxes of an image in LDS; they are instantiated for a capacity of
+// DH_MAX_GT (every P <= 128 runs with the footprint it always had) and of DH_MAX_GT_WIDE (20 KiB of CnGt / FcGt, 28 KiB of YlGt), picked by P in the entry
+// points.  odtk_yolov2_loss keeps DH_MAX_GT.
+constexpr int DH_MAX_GT_WIDE = 1024;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float log_sigmoidf_(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
@@ -112,8 +116,9 @@ __global__ void __launch_bounds__(64) centernet_prep_kernel(const CnArgs a) {
 }
 
 // penalty-reduced focal loss over the heat map (CenterNet.py:211-251), one thread per (pixel, class) element
+template <int CAP>
 __global__ void __launch_bounds__(DH_THREADS) centernet_heat_kernel(const CnArgs a) {
-    __shared__ CnGt sg[DH_MAX_GT];
+    __shared__ CnGt sg[CAP];
     __shared__ float red[DH_THREADS / 64];
     const int n = blockIdx.y;
     const int G = (int)a.info[n * 4 + 0];
@@ -337,9 +342,9 @@ __device__ __forceinline__ FcTarget fcos_target(const FcGt* sg, int M, float gy,
 }
 
 // PASS 0: loss sums per workgroup;  PASS 1: gradients (needs the per-level 1 / sum(heatmap_gt) of pass 0)
-template <int PASS>
+template <int PASS, int CAP>
 __global__ void __launch_bounds__(DH_THREADS) fcos_level_kernel(const FcArgs a) {
-    __shared__ FcGt sg[DH_MAX_GT];
+    __shared__ FcGt sg[CAP];
     __shared__ float red[DH_THREADS / 64];
     const int n = blockIdx.y;
     int l = 0;
@@ -450,9 +455,9 @@ __device__ __forceinline__ FcTargetW fcos_target_wide(const FcGt* sg, int M, flo
     return t;
 }
 
-template <int PASS>
+template <int PASS, int CAP>
 __global__ void __launch_bounds__(DH_THREADS) fcos_level_wide_kernel(const FcArgs a) {
-    __shared__ FcGt sg[DH_MAX_GT];
+    __shared__ FcGt sg[CAP];
     __shared__ float red[DH_THREADS / 64];
     const int n = blockIdx.y;
     int l = 0;
@@ -537,8 +542,9 @@ __global__ void __launch_bounds__(DH_THREADS) fcos_level_wide_kernel(const FcArg
 }
 
 // per (image, level) sums in workgroup order; loss[n] = sum over active levels of (iou + heat + centre) / sum(hm)
+template <int CAP>
 __global__ void __launch_bounds__(64) fcos_reduce_kernel(const FcArgs a) {
-    __shared__ FcGt sg[DH_MAX_GT];
+    __shared__ FcGt sg[CAP];
     const int n = blockIdx.x;
     float total = 0.f;
     for (int l = 0; l < FC_LEVELS; ++l) {
@@ -609,8 +615,9 @@ struct YlGt { float y1, x1, y2, x2, area; int cy, cx; };
 __device__ __forceinline__ float bce_logits(float x, float z) { return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x))); }
 
 // no-object term: every prior of every cell that holds no ground-truth centre (YOLOv3.py:126-131, :247-306)
+template <int CAP>
 __global__ void __launch_bounds__(DH_THREADS) yolov3_noobj_kernel(const YlArgs a) {
-    __shared__ YlGt sg[DH_MAX_GT];
+    __shared__ YlGt sg[CAP];
     __shared__ float red[DH_THREADS / 64];
     __shared__ int sG;
     const int n = blockIdx.y;
@@ -772,7 +779,8 @@ extern "C" int odtk_centernet_loss(const float* keypoints, const float* offset, 
                                    float* d_offset, float* d_size, void* workspace, void* stream) {
     ODTK_REQUIRE(keypoints && offset && size && gt && loss_parts && d_keypoints && d_offset && d_size && workspace,
                  "centernet_loss: null pointer");
-    ODTK_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && P > 0 && P <= DH_MAX_GT, "centernet_loss: N=%d H=%d W=%d C=%d P=%d out of range", N, H, W, C, P);
+    ODTK_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && P > 0, "centernet_loss: N=%d H=%d W=%d C=%d P=%d out of range", N, H, W, C, P);
+    ODTK_REQUIRE(P <= DH_MAX_GT_WIDE, "centernet_loss: P=%d ground-truth rows per image, at most %d", P, DH_MAX_GT_WIDE);
     hipStream_t st = (hipStream_t)stream;
     CnArgs a;
     a.keypoints = keypoints; a.offset = offset; a.size = size; a.gt = gt; a.N = N; a.H = H; a.W = W; a.C = C; a.P = P;
@@ -784,7 +792,8 @@ extern "C" int odtk_centernet_loss(const float* keypoints, const float* offset, 
     if (int e = zero_async(d_offset, (size_t)N * H * W * 2 * sizeof(float), st)) return e;
     if (int e = zero_async(d_size, (size_t)N * H * W * 2 * sizeof(float), st)) return e;
     hipLaunchKernelGGL(centernet_prep_kernel, dim3(N), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(centernet_heat_kernel, dim3(a.nblk, N), dim3(DH_THREADS), 0, st, a);
+    if (P <= DH_MAX_GT) hipLaunchKernelGGL(centernet_heat_kernel<DH_MAX_GT>, dim3(a.nblk, N), dim3(DH_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(centernet_heat_kernel<DH_MAX_GT_WIDE>, dim3(a.nblk, N), dim3(DH_THREADS), 0, st, a);
     hipLaunchKernelGGL(centernet_final_kernel, dim3(N), dim3(DH_THREADS), 0, st, a);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
@@ -832,6 +841,17 @@ static int fcos_fill(FcArgs& a, const int* shapes, int N, int C, int P) {
     return ODTK_OK;
 }
 
+// the three launches of odtk_fcos_loss with CAP staged boxes; WIDE: more classes than one 64-bit heat-map word holds
+template <int CAP, bool WIDE>
+static void fcos_launch(const FcArgs& a, hipStream_t st) {
+    const dim3 grid(a.boff[FC_LEVELS], a.N);
+    auto pass0 = WIDE ? fcos_level_wide_kernel<0, CAP> : fcos_level_kernel<0, CAP>;
+    auto pass1 = WIDE ? fcos_level_wide_kernel<1, CAP> : fcos_level_kernel<1, CAP>;
+    hipLaunchKernelGGL(pass0, grid, dim3(DH_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fcos_reduce_kernel<CAP>, dim3(a.N), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(pass1, grid, dim3(DH_THREADS), 0, st, a);
+}
+
 extern "C" long long odtk_fcos_workspace_bytes(const int* shapes, int N) {
     long long blocks = 0;
     for (int l = 0; l < FC_LEVELS; ++l) blocks += ((long long)shapes[2 * l] * shapes[2 * l + 1] + DH_THREADS - 1) / DH_THREADS;
@@ -842,8 +862,8 @@ extern "C" int odtk_fcos_loss(const float* const* conf, const float* const* reg,
                               const float* gt, int N, int C, int P, float grad_scale, float* loss, float* const* d_conf,
                               float* const* d_reg, float* const* d_center, void* workspace, void* stream) {
     ODTK_REQUIRE(conf && reg && center && shapes && gt && loss && d_conf && d_reg && d_center && workspace, "fcos_loss: null pointer");
-    ODTK_REQUIRE(N > 0 && C > 0 && C <= FC_MAXC && P > 0 && P <= DH_MAX_GT, "fcos_loss: N=%d C=%d P=%d out of range (C <= %d, P <= %d)", N, C, P, FC_MAXC,
-                 DH_MAX_GT);
+    ODTK_REQUIRE(N > 0 && C > 0 && C <= FC_MAXC && P > 0 && P <= DH_MAX_GT_WIDE, "fcos_loss: N=%d C=%d P=%d out of range (C <= %d, P <= %d)", N, C, P, FC_MAXC,
+                 DH_MAX_GT_WIDE);
     FcArgs a;
     memset(&a, 0, sizeof(a));
     if (int e = fcos_fill(a, shapes, N, C, P)) return e;
@@ -857,11 +877,8 @@ extern "C" int odtk_fcos_loss(const float* const* conf, const float* const* reg,
     a.lsum = a.parts + (size_t)N * a.boff[FC_LEVELS] * 4;
     hipStream_t st = (hipStream_t)stream;
     const bool wide = C > DH_MAXC;                       // more classes than one 64-bit heat-map word holds
-    if (wide) hipLaunchKernelGGL(fcos_level_wide_kernel<0>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(fcos_level_kernel<0>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
-    hipLaunchKernelGGL(fcos_reduce_kernel, dim3(N), dim3(64), 0, st, a);
-    if (wide) hipLaunchKernelGGL(fcos_level_wide_kernel<1>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(fcos_level_kernel<1>, dim3(a.boff[FC_LEVELS], N), dim3(DH_THREADS), 0, st, a);
+    if (P <= DH_MAX_GT) { if (wide) fcos_launch<DH_MAX_GT, true>(a, st); else fcos_launch<DH_MAX_GT, false>(a, st); }
+    else { if (wide) fcos_launch<DH_MAX_GT_WIDE, true>(a, st); else fcos_launch<DH_MAX_GT_WIDE, false>(a, st); }
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }
@@ -920,7 +937,8 @@ extern "C" int odtk_yolov3_loss(const float* const* pred, const int* shapes, con
     YlArgs a;
     memset(&a, 0, sizeof(a));
     if (int e = yolo_fill(a, pred, shapes, priors, head_stride, nullptr, N, num_priors, C)) return e;
-    ODTK_REQUIRE(gt && loss_parts && d_pred && workspace && pad > 0 && pad <= DH_MAX_GT, "yolov3_loss: bad argument (pad=%d)", pad);
+    ODTK_REQUIRE(gt && loss_parts && d_pred && workspace && pad > 0, "yolov3_loss: bad argument (pad=%d)", pad);
+    ODTK_REQUIRE(pad <= DH_MAX_GT_WIDE, "yolov3_loss: pad=%d ground-truth rows per image, at most %d", pad, DH_MAX_GT_WIDE);
     hipStream_t st = (hipStream_t)stream;
     for (int l = 0; l < YL_HEADS; ++l) {
         ODTK_REQUIRE(d_pred[l], "yolov3_loss: null gradient pointer %d", l);
@@ -929,7 +947,8 @@ extern "C" int odtk_yolov3_loss(const float* const* pred, const int* shapes, con
     }
     a.gt = gt; a.pad = pad; a.coord_scale = coord_scale; a.noobj_scale = noobj_scale; a.obj_scale = obj_scale;
     a.class_scale = class_scale; a.grad_scale = grad_scale; a.parts = (float*)workspace; a.loss_parts = loss_parts;
-    hipLaunchKernelGGL(yolov3_noobj_kernel, dim3(a.boff[YL_HEADS], N), dim3(DH_THREADS), 0, st, a);
+    if (pad <= DH_MAX_GT) hipLaunchKernelGGL(yolov3_noobj_kernel<DH_MAX_GT>, dim3(a.boff[YL_HEADS], N), dim3(DH_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(yolov3_noobj_kernel<DH_MAX_GT_WIDE>, dim3(a.boff[YL_HEADS], N), dim3(DH_THREADS), 0, st, a);
     hipLaunchKernelGGL(yolov3_pos_kernel, dim3(N), dim3(64), 0, st, a);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;

@@ -16,7 +16,11 @@ namespace odtk { namespace cv { int misc_scratch(size_t bytes, hipStream_t st, c
 namespace odtk {
 namespace {
 
-constexpr int RL_MAX_LEVELS = 8, RL_MAX_NA = 16, RL_MAX_GT = 128, RL_THREADS = 256, RL_MAXC = 32;
+constexpr int RL_MAX_LEVELS = 8, RL_MAX_NA = 16, RL_THREADS = 256, RL_MAXC = 32;
+// Ground-truth rows per image: the matching kernels are instantiated for a capacity of RL_MAX_GT (every P <= 128 runs with the LDS footprint it always
+// had) and of RL_MAX_GT_WIDE (20 KiB of boxes + 32 KiB of per-wave partial arg-maxima in retina_iou_kernel); odtk_retina_match picks by P.
+constexpr int RL_MAX_GT = 128, RL_MAX_GT_WIDE = 1024;
+constexpr int RL_BEST_THREADS = 128;               // workgroup of the best-rows kernels: they walk the G boxes in strides of it
 constexpr int RL_LOSS_TILES = 8;                   // anchor tiles per workgroup of the loss pass (2 atomics per workgroup)
 constexpr int RL_TILES_PER_BLOCK = 4;              // anchor tiles per workgroup of the IoU pass (amortises the GT set-up)
 
@@ -82,16 +86,17 @@ __device__ int gt_count(const float* gt, int P, float* s_val, int* s_idx) {
 }
 
 // Pass 1: per anchor max / first arg-max over the GT; per (tile, GT) first arg-max over the tile's anchors.
+template <int CAP>
 __global__ void __launch_bounds__(RL_THREADS) retina_iou_kernel(
     const float* __restrict__ y1x1, const float* __restrict__ y2x2, const float* __restrict__ hw, int A,
     const float* __restrict__ gt, int P, float* __restrict__ maxiou, int* __restrict__ rgindex,
     float* __restrict__ part_iou, int* __restrict__ part_idx, unsigned char* __restrict__ status,
     int* __restrict__ counts) {
-    __shared__ GtBox s_g[RL_MAX_GT];
+    __shared__ GtBox s_g[CAP];
     __shared__ float s_val[RL_THREADS / 64];
     __shared__ int s_idx[RL_THREADS / 64];
-    __shared__ float s_wv[RL_THREADS / 64][RL_MAX_GT];
-    __shared__ int s_wi[RL_THREADS / 64][RL_MAX_GT];
+    __shared__ float s_wv[RL_THREADS / 64][CAP];
+    __shared__ int s_wi[RL_THREADS / 64][CAP];
     const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ntile = (A + RL_THREADS - 1) / RL_THREADS;
     const float* g = gt + (size_t)n * P * 5;
@@ -152,6 +157,7 @@ __global__ void __launch_bounds__(RL_THREADS) retina_iou_kernel(
 // Pass 2 (one workgroup per image): best anchor per GT = first arg-max over all tiles (tiles in ascending order,
 // strict >), then the best anchors leave the "other" set (:397-407): status 3, counts corrected once per DISTINCT
 // best anchor.  counts[n] = {rows of the positive set = G + #(IoU > 0.5 among the others), #negatives, min(3 * positives, negatives), 0}.
+template <int CAP>
 __global__ void __launch_bounds__(RL_THREADS) retina_status_kernel(
     const float* __restrict__ gt, int P, int A, int ntile, const float* __restrict__ part_iou,
     const int* __restrict__ part_idx, const float* __restrict__ maxiou, int* __restrict__ ngt, int* __restrict__ best,
@@ -160,7 +166,7 @@ __global__ void __launch_bounds__(RL_THREADS) retina_status_kernel(
     __shared__ int s_idx[RL_THREADS / 64];
     __shared__ float s_pv[RL_THREADS / 64];
     __shared__ int s_pi[RL_THREADS / 64];
-    __shared__ int s_best[RL_MAX_GT];
+    __shared__ int s_best[CAP];
     __shared__ int s_fix[2];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int G = gt_count(gt + (size_t)n * P * 5, P, s_val, s_idx);
@@ -350,29 +356,43 @@ __global__ void __launch_bounds__(RL_THREADS) retina_loss_kernel(const RLossArgs
 
 // the G "best" rows of every image (duplicates allowed: two GT may pick one anchor) -- accumulated on top of
 // the zeros written by retina_loss_kernel, hence a second launch
-__global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_kernel(const RLossArgs a, const int nparts) {
-    __shared__ float s_w[2][RL_MAX_GT / 64];
-    const int n = blockIdx.x, g = threadIdx.x;
+// STRIDED = false (P <= 128): one box per thread, the kernel every result so far came from; true: thread t takes boxes t, t + 128, ... in ascending order
+template <bool STRIDED>
+__global__ void __launch_bounds__(RL_BEST_THREADS) retina_best_rows_kernel(const RLossArgs a, const int nparts) {
+    __shared__ float s_w[2][RL_BEST_THREADS / 64];
+    const int n = blockIdx.x, tid = threadIdx.x;
     const int G = a.ngt[n];
     float conf = 0.f, coord = 0.f;
     const float inv_np = 1.f / (float)a.counts[n * 4 + 0];
-    if (g < G) {
-        const int an = a.best[(size_t)n * a.P + g];
-        const size_t row = (size_t)n * a.A + an;
-        const int label = (int)a.gt[((size_t)n * a.P + g) * 5 + 4];
-        const float gs = a.grad_scale * inv_np;
-        conf = focal_row(a, a.pconf + row * a.C, a.dconf + row * a.C, label, gs, true);
-        coord = box_row(a, n, an, g, a.pbox + row * 4, a.dbox + row * 4, gs, true);
+    if (!STRIDED) {
+        const int g = tid;
+        if (g < G) {
+            const int an = a.best[(size_t)n * a.P + g];
+            const size_t row = (size_t)n * a.A + an;
+            const int label = (int)a.gt[((size_t)n * a.P + g) * 5 + 4];
+            const float gs = a.grad_scale * inv_np;
+            conf = focal_row(a, a.pconf + row * a.C, a.dconf + row * a.C, label, gs, true);
+            coord = box_row(a, n, an, g, a.pbox + row * 4, a.dbox + row * 4, gs, true);
+        }
+    } else {
+        for (int g = tid; g < G; g += RL_BEST_THREADS) {
+            const int an = a.best[(size_t)n * a.P + g];
+            const size_t row = (size_t)n * a.A + an;
+            const int label = (int)a.gt[((size_t)n * a.P + g) * 5 + 4];
+            const float gs = a.grad_scale * inv_np;
+            conf += focal_row(a, a.pconf + row * a.C, a.dconf + row * a.C, label, gs, true);
+            coord += box_row(a, n, an, g, a.pbox + row * 4, a.dbox + row * 4, gs, true);
+        }
     }
     for (int o = 32; o > 0; o >>= 1) { conf += __shfl_xor(conf, o); coord += __shfl_xor(coord, o); }
-    if ((g & 63) == 0) { s_w[0][g >> 6] = conf * inv_np; s_w[1][g >> 6] = coord * inv_np; }
+    if ((tid & 63) == 0) { s_w[0][tid >> 6] = conf * inv_np; s_w[1][tid >> 6] = coord * inv_np; }
     __syncthreads();
-    if (g < 2) {                                       // fixed order: the loss pass's workgroups, then this launch's waves
+    if (tid < 2) {                                     // fixed order: the loss pass's workgroups, then this launch's waves
         float t = 0.f;
-        const float* pp = a.parts + (size_t)n * nparts * 2 + g;
+        const float* pp = a.parts + (size_t)n * nparts * 2 + tid;
         for (int b = 0; b < nparts; ++b) t += pp[2 * b];
-        for (int w = 0; w < RL_MAX_GT / 64; ++w) t += s_w[g][w];
-        a.loss_parts[n * 2 + g] = t;
+        for (int w = 0; w < RL_BEST_THREADS / 64; ++w) t += s_w[tid][w];
+        a.loss_parts[n * 2 + tid] = t;
     }
 }
 
@@ -495,14 +515,14 @@ __global__ void __launch_bounds__(RL_THREADS) retina_loss_wide_kernel(const RLos
 
 // retina_best_rows_kernel for groups: 8 ground-truth rows per pass, the group's first lane carries the sums
 template <int K>
-__global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_wide_kernel(const RLossArgs a, const int nparts) {
-    __shared__ float s_w[2][RL_MAX_GT / 64];
+__global__ void __launch_bounds__(RL_BEST_THREADS) retina_best_rows_wide_kernel(const RLossArgs a, const int nparts) {
+    __shared__ float s_w[2][RL_BEST_THREADS / 64];
     const int n = blockIdx.x, tid = threadIdx.x, j = tid & (wr::L - 1), q = tid / wr::L;
     const int G = a.ngt[n];
     float conf = 0.f, coord = 0.f;
     const float inv_np = 1.f / (float)a.counts[n * 4 + 0];
     const float gs = a.grad_scale * inv_np;
-    for (int g0 = 0; g0 < G; g0 += RL_MAX_GT / wr::L) {
+    for (int g0 = 0; g0 < G; g0 += RL_BEST_THREADS / wr::L) {
         const int g = g0 + q;
         const bool on = g < G;
         const int an = on ? a.best[(size_t)n * a.P + g] : 0;
@@ -521,7 +541,7 @@ __global__ void __launch_bounds__(RL_MAX_GT) retina_best_rows_wide_kernel(const 
         float t = 0.f;
         const float* pp = a.parts + (size_t)n * nparts * 2 + tid;
         for (int b = 0; b < nparts; ++b) t += pp[2 * b];
-        for (int w = 0; w < RL_MAX_GT / 64; ++w) t += s_w[tid][w];
+        for (int w = 0; w < RL_BEST_THREADS / 64; ++w) t += s_w[tid][w];
         a.loss_parts[n * 2 + tid] = t;
     }
 }
@@ -533,7 +553,7 @@ static int retina_loss_wide_launch(RLossArgs& a, hipStream_t st) {
     if (int e = cv::misc_scratch((size_t)a.N * nparts * 2 * sizeof(float), st, &parts)) return e;
     a.parts = (float*)parts;
     hipLaunchKernelGGL(retina_loss_wide_kernel<K>, dim3(nparts, a.N), dim3(RL_THREADS), 0, st, a);
-    hipLaunchKernelGGL(retina_best_rows_wide_kernel<K>, dim3(a.N), dim3(RL_MAX_GT), 0, st, a, nparts);
+    hipLaunchKernelGGL(retina_best_rows_wide_kernel<K>, dim3(a.N), dim3(RL_BEST_THREADS), 0, st, a, nparts);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }
@@ -644,21 +664,30 @@ extern "C" long long odtk_retina_match_workspace_bytes(int A, int N, int P) {
     return (long long)N * A * 4 + 2ll * N * ntile * P * 4;
 }
 
+template <int CAP>
+static void retina_match_launch(const float* y1x1, const float* y2x2, const float* hw, int A, const float* gt, int N, int P, int* ngt, int* best,
+                                unsigned char* status, int* rgindex, int* counts, float* maxiou, float* part_iou, int* part_idx, hipStream_t st) {
+    const int ntile = ceil_div(A, RL_THREADS);
+    hipLaunchKernelGGL(retina_iou_kernel<CAP>, dim3(ceil_div(ntile, RL_TILES_PER_BLOCK), N), dim3(RL_THREADS), 0, st, y1x1, y2x2, hw, A, gt, P, maxiou, rgindex,
+                       part_iou, part_idx, status, counts);
+    hipLaunchKernelGGL(retina_status_kernel<CAP>, dim3(N), dim3(RL_THREADS), 0, st, gt, P, A, ntile, part_iou, part_idx, maxiou,
+                       ngt, best, status, counts);
+}
+
 extern "C" int odtk_retina_match(const float* y1x1, const float* y2x2, const float* hw, int A, const float* gt, int N,
                                  int P, int* ngt, int* best, unsigned char* status, int* rgindex, int* counts,
                                  void* workspace, void* stream) {
     ODTK_REQUIRE(y1x1 && y2x2 && hw && gt && ngt && best && status && rgindex && counts && workspace, "retina_match: null pointer");
-    ODTK_REQUIRE(A > 0 && N > 0 && P > 0 && P <= RL_MAX_GT, "retina_match: A=%d N=%d P=%d out of range", A, N, P);
+    ODTK_REQUIRE(A > 0 && N > 0 && P > 0, "retina_match: A=%d N=%d P=%d out of range", A, N, P);
+    ODTK_REQUIRE(P <= RL_MAX_GT_WIDE, "retina_match: P=%d ground-truth rows per image, at most %d", P, RL_MAX_GT_WIDE);
     const int ntile = ceil_div(A, RL_THREADS);
     float* maxiou = (float*)workspace;
     float* part_iou = maxiou + (size_t)N * A;
     int* part_idx = (int*)(part_iou + (size_t)N * ntile * P);
     hipStream_t st = (hipStream_t)stream;
     if (int e = zero_async(counts, (size_t)N * 4 * sizeof(int), st)) return e;
-    hipLaunchKernelGGL(retina_iou_kernel, dim3(ceil_div(ntile, RL_TILES_PER_BLOCK), N), dim3(RL_THREADS), 0, st, y1x1, y2x2, hw, A, gt, P, maxiou, rgindex,
-                       part_iou, part_idx, status, counts);
-    hipLaunchKernelGGL(retina_status_kernel, dim3(N), dim3(RL_THREADS), 0, st, gt, P, A, ntile, part_iou, part_idx, maxiou,
-                       ngt, best, status, counts);
+    if (P <= RL_MAX_GT) retina_match_launch<RL_MAX_GT>(y1x1, y2x2, hw, A, gt, N, P, ngt, best, status, rgindex, counts, maxiou, part_iou, part_idx, st);
+    else retina_match_launch<RL_MAX_GT_WIDE>(y1x1, y2x2, hw, A, gt, N, P, ngt, best, status, rgindex, counts, maxiou, part_iou, part_idx, st);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }
@@ -669,7 +698,8 @@ extern "C" int odtk_retina_loss(const float* pconf, const float* pbox, int N, in
                                 float gamma, float grad_scale, float* loss_parts, float* dconf, float* dbox, void* stream) {
     ODTK_REQUIRE(pconf && pbox && yx && hw && gt && ngt && best && status && rgindex && counts && loss_parts && dconf && dbox,
                  "retina_loss: null pointer");
-    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && P > 0 && P <= RL_MAX_GT, "retina_loss: C=%d P=%d unsupported (2 <= C <= %d, P <= %d)", C, P, wr::MAXC, RL_MAX_GT);
+    ODTK_REQUIRE(C > 1 && C <= wr::MAXC && P > 0 && P <= RL_MAX_GT_WIDE, "retina_loss: C=%d P=%d unsupported (2 <= C <= %d, P <= %d)", C, P, wr::MAXC,
+                 RL_MAX_GT_WIDE);
     hipStream_t st = (hipStream_t)stream;
     RLossArgs a;
     a.pconf = pconf; a.pbox = pbox; a.N = N; a.A = A; a.C = C; a.yx = yx; a.hw = hw; a.gt = gt; a.P = P;
@@ -683,7 +713,8 @@ extern "C" int odtk_retina_loss(const float* pconf, const float* pbox, int N, in
     if (int e = cv::misc_scratch((size_t)N * nparts * 2 * sizeof(float), st, &parts)) return e;
     a.parts = (float*)parts;
     hipLaunchKernelGGL(retina_loss_kernel, dim3(nparts, N), dim3(RL_THREADS), 0, st, a);
-    hipLaunchKernelGGL(retina_best_rows_kernel, dim3(N), dim3(RL_MAX_GT), 0, st, a, nparts);
+    if (P <= RL_MAX_GT) hipLaunchKernelGGL(retina_best_rows_kernel<false>, dim3(N), dim3(RL_BEST_THREADS), 0, st, a, nparts);
+    else hipLaunchKernelGGL(retina_best_rows_kernel<true>, dim3(N), dim3(RL_BEST_THREADS), 0, st, a, nparts);
     ODTK_LAUNCH_CHECK();
     return ODTK_OK;
 }

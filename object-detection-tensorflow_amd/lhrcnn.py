@@ -114,6 +114,7 @@ class _Stage:
 
 class LHRCNN(RefineDet320):
     NAME = 'LHRCNN'
+    GT_ROWS_LIMIT = ops.GT_ROWS_MAX_NARROW  # odtk_lhrcnn_match / odtk_lhrcnn_rpn_loss stage 128 boxes
     # Training default: the EXACT f32 engine (round 5).  'f32x3' (compute_dtype='f32x3': f32 tensors, convolutions / dense layers as three bf16 MFMA products, 440 -> 595
     # images/s) stays opt-in for this class: it is the one class the gradient-direction gate (tools/bf16_after_training.py, profiles/r04x_gate_f32x3_all_classes.md) was
     # never run for, and its second training step sits 6-9 % off the oracle's loss where the exact engine holds 5e-2 (tests/test_gpu_lhrcnn.py).

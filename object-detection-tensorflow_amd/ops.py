@@ -419,6 +419,20 @@ def check_num_classes(who, num_classes, background):
                          + (f' ({MAX_ROW_LOGITS} logits per row with the background)' if background else ''))
 
 
+# Ground-truth rows per image (P = gt.shape[1], the generator's pad_truth_to) the matching and loss entry points stage: odtk_ssd_match, odtk_retina_match
+# (also in front of odtk_refinedet_loss), odtk_retina_loss, odtk_fcos_loss, odtk_centernet_loss, odtk_yolov3_loss take GT_ROWS_MAX; odtk_yolov2_loss and
+# the odtk_lhrcnn_* entry points GT_ROWS_MAX_NARROW (include/odtk.h, "Ground-truth rows").
+GT_ROWS_MAX = 1024
+GT_ROWS_MAX_NARROW = 128
+
+
+def check_gt_rows(who, shape, limit):
+    """set_batch's check of the ground truth [N, P, 5 or 6] against the limit of the class's box-side kernels, before anything is launched"""
+    if len(shape) >= 2 and not 1 <= shape[1] <= limit:
+        raise ValueError(f'{who}: ground truth of shape {tuple(shape)}: P={shape[1]} rows per image out of range, this class takes 1..{limit} '
+                         f'(pad_truth_to <= {limit})')
+
+
 def ssd_loss(pred, Cn, yx, hw, gt, ngt, best, status, rgindex, counts, negloss, sel_idx, sel_cnt, grad_scale,
              loss_parts, dpred):
     """SSD300.py:430-450 for the batch; pred [N, A, ld] with Cn <= MAX_ROW_LOGITS logits (background last) and 4 regressions per row, ld >= Cn + 4"""

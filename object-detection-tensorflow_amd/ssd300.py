@@ -901,6 +901,7 @@ class SSD300(BatchedInference, F32Warmup, DetectorBase):
             self.images.copy_(images, non_blocking=True)
         gt = torch.as_tensor(ground_truth, dtype=torch.float32)
         if self.gt is None or self.gt.shape != gt.shape:
+            ops.check_gt_rows(type(self).__name__, gt.shape, self.GT_ROWS_LIMIT)
             self.gt = torch.zeros(gt.shape, device=self.dev)
             self._graphs_invalidate()                 # captured launches hold the old pointer / pad length
         self.gt.copy_(gt, non_blocking=True)

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import torch
 
-from . import heads
+from . import heads, ops
 from .refinedet import RefineDet320
 from .voc_eval import EvaluateMixin
 
@@ -62,6 +62,7 @@ def reference_variable_map(num_layers_backbone=18):
 class YOLOv2(RefineDet320):
     L2_AFTER = None
     NAME = 'YOLOv2'
+    GT_ROWS_LIMIT = ops.GT_ROWS_MAX_NARROW  # odtk_yolov2_loss stages 128 boxes
     DEFAULT_ENGINE = 'bf16'                 # passes the gate (filter-gradient cosine vs f32 after 300 f32 steps: input side 0.93, minimum 0.91)
 
     def __init__(self, config, data_provider):
