@@ -458,6 +458,28 @@ int odtk_detection_pack(const int* nms_idx, const int* nms_cnt, int N, int num_c
                         const float* boxes, long long box_istride, int* counts, int* offsets, float* scores, float* bbox, int* class_id,
                         void* stream);
 
+/* Soft-NMS (Bodla et al. 2017) for N * num_classes problems in one launch (csrc/soft_nms.hip): the operands, their addressing and the limits of
+ * odtk_nms_image_class (n <= 32768, N * num_classes <= 65535, n_dev, boxes 16-byte aligned), plus out_score [N][num_classes][cap].  A row is live when it is
+ * valid and its score is above -inf (NaN excluded), the rule of odtk_nms_image_class.  Per problem, until min(max_out, cap) picks are made: m = the live row
+ * with the largest CURRENT score (the lower row on equal scores); stop when none is live; out_idx[k] = m, out_score[k] = its current (decayed) score; m
+ * leaves; every live j with iou = IoU(box m, box j) (the IoU of odtk_nms_batched: corners normalised, 0 when an area is <= 0) is decayed by `method`:
+ *   0 hard      dead if iou > iou_threshold (greedy NMS: the picks and counts of odtk_nms_image_class, out_score = their original scores);
+ *   1 linear    s_j = s_j * (1 - iou) if iou > iou_threshold;
+ *   2 gaussian  s_j = s_j * expf(-(iou * iou) / sigma), for every j (sigma > 0);
+ * with methods 1 and 2 every live j whose score is then not >= min_score is dead.  float32 in exactly this order, no contraction.  out_cnt = the picks made;
+ * slots of out_idx / out_score behind the count are not written.  One workgroup per problem, the live scores in LDS (up to 2048 live rows compacted with
+ * their boxes, 48 KiB; more: all n scores, 4 n bytes, the boxes read from global memory -- slower, never dropped); no atomics, identical bytes on every run. */
+int odtk_soft_nms_image_class(const float* boxes, long long box_istride, const float* scores, long long score_istride, long long score_cstride,
+                              int score_estride, const unsigned char* valid, long long valid_istride, long long valid_cstride, int valid_estride,
+                              int valid_value, int n, const int* n_dev, int N, int num_classes, int max_out, int method, float iou_threshold, float sigma,
+                              float min_score, int* out_idx, float* out_score, int cap, int* out_cnt, void* stream);
+
+/* odtk_detection_pack with the scores taken from the soft-NMS table: scores[k] = nms_score[(img*num_classes + c)*cap + j] for pick j of class c of image
+ * img; counts, offsets, bbox, class_id and the row order are those of odtk_detection_pack on the same tables (it runs underneath).  N <= 1024. */
+int odtk_detection_pack_scored(const int* nms_idx, const int* nms_cnt, const float* nms_score, int N, int num_classes, int cap, const float* conf,
+                               long long conf_istride, int ldc, const float* boxes, long long box_istride, int* counts, int* offsets, float* scores,
+                               float* bbox, int* class_id, void* stream);
+
 /* ---- Ground-truth rows ----
  * Every matching and loss entry point takes the ground truth as gt [N][P][5] (P = the generator's pad_truth_to; the rows in front of the first minimum of
  * column 0 are the boxes) and stages an image's boxes in LDS.  odtk_ssd_match, odtk_retina_match (also in front of odtk_refinedet_loss), odtk_retina_loss,

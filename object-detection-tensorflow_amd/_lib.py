@@ -163,6 +163,8 @@ SIGNATURES = {
     "odtk_compact_rows": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "odtk_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "odtk_detection_pack": (_i, [_vp, _vp, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "odtk_soft_nms_image_class": (_i, [_vp, _ll, _vp, _ll, _ll, _i, _vp, _ll, _ll, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp]),
+    "odtk_detection_pack_scored": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
     "odtk_ssd_decode": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "odtk_depthwise_conv": (_i, [_vp, _i, _vp, _vp, _i] + [_i] * 9 + [_vp]),
     "odtk_depthwise_wgrad": (_i, [_vp, _i, _vp, _i, _vp] + [_i] * 7 + [_vp]),

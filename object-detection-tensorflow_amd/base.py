@@ -88,6 +88,7 @@ class DetectorBase:
             self.nms_score_threshold = config['nms_score_threshold']
             self.nms_max_boxes = config['nms_max_boxes']
             self.nms_iou_threshold = config['nms_iou_threshold']
+        self._read_nms_method(config, nms)
         self.verbose = bool(config.get('verbose', True))
         self.dev = torch.device(config.get('device', 'cuda:0'))
         if self.mode == 'train':
@@ -108,6 +109,37 @@ class DetectorBase:
         self.loss_divisor_batch = self.batch_size
         if self.dev.type == 'cuda':          # (a 'cpu' device only gets past ops._p with the mocked library of tests/mock_ops.py: host-logic tests)
             torch.cuda.set_device(self.dev)
+
+    def _read_nms_method(self, config, nms):
+        """config['nms_method']: 'hard' (default: the reference's greedy NMS, today's launches) | 'linear' | 'gaussian' (soft-NMS, odtk_soft_nms_image_class);
+        config['soft_nms_sigma'] (default 0.5, > 0) and config['soft_nms_min_score'] (>= 0; default: whatever nms_score_threshold is at the time of the call).
+        A class without an NMS (CenterNet: top-k decode) takes 'hard' only."""
+        method = config.get('nms_method', 'hard')
+        if not isinstance(method, str) or method not in ops.NMS_METHODS:
+            raise ValueError(f"nms_method must be 'hard', 'linear' or 'gaussian', not {method!r}")
+        if not nms:
+            if method != 'hard':
+                raise ValueError(f"nms_method = {method!r}: {type(self).__name__} has no NMS (its decode is a top-k over peaks); only 'hard' is accepted")
+            return
+
+        def number(key, default, ok, rule):
+            if key not in config:
+                return default
+            v = config[key]
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not ok(v):
+                raise ValueError(f"{key} must be a number {rule}, not {v!r}")
+            return float(v)
+        self.nms_method = method
+        self.soft_nms_sigma = number('soft_nms_sigma', 0.5, lambda v: v > 0, '> 0')
+        self._soft_nms_min_score = number('soft_nms_min_score', None, lambda v: v >= 0, '>= 0')
+
+    @property
+    def soft_nms_min_score(self):
+        return self.nms_score_threshold if self._soft_nms_min_score is None else self._soft_nms_min_score
+
+    def _nms_params(self):
+        """what heads.BatchedTail and heads._per_class_nms take beside the IoU threshold"""
+        return dict(method=self.nms_method, sigma=self.soft_nms_sigma, min_score=self.soft_nms_min_score)
 
     def _set_engine(self, engine):
         """'bf16' | 'f32' | 'f32x3': f32 tensors, convolution descriptors of dtype ODTK_F32X3 (three bf16 MFMA products per f32 product where that is

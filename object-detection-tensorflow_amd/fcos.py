@@ -242,7 +242,7 @@ class FCOS(EvaluateMixin, F32Warmup, graph.SharedGradients, DetectorBase):
         self._stage_test_image(images)
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
         scores, bbox, cid = heads.fcos_detect([t[0] for t in self.conf], [t[0] for t in self.reg], [t[0] for t in self.center],
-                                              self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold)
+                                              self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold, **self._nms_params())
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ checkpoints / data parallel

@@ -17,8 +17,9 @@ from .voc_eval import EvaluateMixin
 NMS_MAX_CANDIDATES = 32768          # odtk_nms_batched: boxes per problem
 
 
-def _per_class_nms(conf, boxes, cand, num_classes, max_boxes, iou_thr):
-    """conf [L, ld] scores (classes 0..num_classes-1 in the first columns), boxes [L, 4], cand [L, ld] uint8."""
+def _per_class_nms(conf, boxes, cand, num_classes, max_boxes, iou_thr, method='hard', sigma=0.5, min_score=0.0):
+    """conf [L, ld] scores (classes 0..num_classes-1 in the first columns), boxes [L, 4], cand [L, ld] uint8.  method 'hard': greedy NMS (odtk_nms_batched);
+    'linear' / 'gaussian': soft-NMS (odtk_soft_nms_image_class at one image), the scores returned are the decayed ones."""
     dev = conf.device
     L, ld = conf.shape
     rows = None
@@ -34,12 +35,18 @@ def _per_class_nms(conf, boxes, cand, num_classes, max_boxes, iou_thr):
     cap = max(int(max_boxes), 1)
     out_idx = torch.zeros(num_classes, cap, dtype=torch.int32, device=dev)
     out_cnt = torch.zeros(num_classes, dtype=torch.int32, device=dev)
-    ops.nms_batched(boxes, 0, conf, 1, ld, cand, 1, ld, 1, L, num_classes, None, 0, int(max_boxes), float(iou_thr), out_idx, cap, out_cnt)
+    soft = method != 'hard'
+    if soft:
+        out_score = torch.zeros(num_classes, cap, device=dev)
+        ops.soft_nms_image_class(boxes, 0, conf, 0, 1, ld, cand, 0, 1, ld, 1, L, None, 1, num_classes, int(max_boxes), ops.NMS_METHODS[method], float(iou_thr),
+                                 float(sigma), float(min_score), out_idx, out_score, cap, out_cnt)
+    else:
+        ops.nms_batched(boxes, 0, conf, 1, ld, cand, 1, ld, 1, L, num_classes, None, 0, int(max_boxes), float(iou_thr), out_idx, cap, out_cnt)
     cnt = out_cnt.cpu().tolist()
     scores, bbox, cid = [], [], []
     for c in range(num_classes):                      # ascending class id, NMS pick order inside (the reference's concat order)
         ids = out_idx[c, : cnt[c]].long()
-        scores.append(conf[ids, c]); bbox.append(boxes[ids])
+        scores.append(out_score[c, : cnt[c]] if soft else conf[ids, c]); bbox.append(boxes[ids])
         cid.append(torch.full((cnt[c],), c, dtype=torch.int32, device=dev))
     return torch.cat(scores), torch.cat(bbox, 0).reshape(-1, 4), torch.cat(cid)
 
@@ -51,10 +58,13 @@ class BatchedTail:
     alone, bit for bit: the same NMS kernels on the same operands, the same order (ascending class id, NMS pick order inside).  Buffers are allocated once
     per (N, A, num_classes, max_boxes).  conf [N, A, ld] scores (classes in the first num_classes columns), boxes [N, A, 4], cand [N, A, ld] uint8.
     The tail also holds what a class's decode writes for it: self.conf [N, A, nc], self.boxes [N, A, 4], self.keep u8 [N, A], self.cand u8 [N, A, nc];
-    bool_cand (YOLOv3: the threshold is one torch.ge): cand is a bool tensor and there is no keep.  `launch_own` runs the tail on them."""
+    bool_cand (YOLOv3: the threshold is one torch.ge): cand is a bool tensor and there is no keep.  `launch_own` runs the tail on them.
+    method 'hard' (default): exactly the launches above.  'linear' / 'gaussian' (with `sigma`, `min_score`): odtk_soft_nms_image_class and
+    odtk_detection_pack_scored in their place -- same picks table, plus out_score [N, nc, cap], the decayed scores the pack hands on."""
 
-    def __init__(self, N, A, num_classes, max_boxes, device, bool_cand=False):
+    def __init__(self, N, A, num_classes, max_boxes, device, bool_cand=False, method='hard', sigma=0.5, min_score=0.0):
         self.N, self.A, self.nc, self.max_boxes = int(N), int(A), int(num_classes), int(max_boxes)
+        self.method, self.sigma, self.min_score = ops.NMS_METHODS[method], float(sigma), float(min_score)
         dev = self.dev = torch.device(device)
         N, A, nc = self.N, self.A, self.nc
         self.conf = torch.zeros(N, A, nc, device=dev)
@@ -73,6 +83,7 @@ class BatchedTail:
             self.c_cand = torch.zeros(N, R, nc, dtype=torch.uint8, device=dev)
         self.out_idx = torch.zeros(N, nc, cap, **i32)
         self.out_cnt = torch.zeros(N, nc, **i32)
+        self.out_score = torch.zeros(N, nc, cap, device=dev) if self.method else None
         # what travels back, one buffer of 4-byte words: counts [N] | offsets [N + 1] | compaction counts [N] | scores [K] | bbox [K, 4] | class_id [K]
         K = self.K = N * nc * cap
         self.words = torch.zeros(3 * N + 1 + 6 * K, **i32)
@@ -96,12 +107,16 @@ class BatchedTail:
             ops.compact_rows(cand, nc, R, self.rows, self.row_cnt)
             ops.gather_rows(self.rows, self.row_cnt, nc, conf, boxes, cand, self.c_conf, self.c_boxes, self.c_cand)
             conf, boxes = self.c_conf, self.c_boxes
-            ops.nms_image_class(boxes, R * 4, conf, R * nc, 1, nc, self.c_cand, R * nc, 1, nc, 1, R, self.row_cnt, N, nc, self.max_boxes, iou_thr,
-                                self.out_idx, self.cap, self.out_cnt)
+            operands = (boxes, R * 4, conf, R * nc, 1, nc, self.c_cand, R * nc, 1, nc, 1, R, self.row_cnt, N, nc, self.max_boxes)
         else:
-            ops.nms_image_class(boxes, A * 4, conf, A * ld, 1, ld, cand, A * ld, 1, ld, 1, A, None, N, nc, self.max_boxes, iou_thr,
-                                self.out_idx, self.cap, self.out_cnt)
-        ops.detection_pack(self.out_idx, self.out_cnt, conf, boxes, self.counts, self.offsets, self.scores, self.bbox, self.class_id)
+            operands = (boxes, A * 4, conf, A * ld, 1, ld, cand, A * ld, 1, ld, 1, A, None, N, nc, self.max_boxes)
+        if self.method:
+            ops.soft_nms_image_class(*operands, self.method, iou_thr, self.sigma, self.min_score, self.out_idx, self.out_score, self.cap, self.out_cnt)
+            ops.detection_pack_scored(self.out_idx, self.out_cnt, self.out_score, conf, boxes, self.counts, self.offsets, self.scores, self.bbox,
+                                      self.class_id)
+        else:
+            ops.nms_image_class(*operands, iou_thr, self.out_idx, self.cap, self.out_cnt)
+            ops.detection_pack(self.out_idx, self.out_cnt, conf, boxes, self.counts, self.offsets, self.scores, self.bbox, self.class_id)
 
     def launch_own(self, iou_thr):
         """launch() on the decode outputs the tail holds itself"""
@@ -218,6 +233,8 @@ class BatchedInference(EvaluateMixin):
         t = self._tail_batched
         if t is None:
             t = self._tail_batched = self._make_tail()
+        if getattr(t, 'method', 0):
+            t.min_score = float(self.soft_nms_min_score)            # (its default follows nms_score_threshold, which may be set between calls)
         self._launch_tail(t)
         return t.read(n)
 
@@ -279,18 +296,19 @@ class RefineDetLoss:
         return self.loss_parts
 
 
-def fcos_detect(conf, reg, center, score_thr, max_boxes, iou_thr):
-    """FCOS.py:197-265.  conf / reg / center: the five level tensors [H, W, C | 4 | 1] of one image; classes 0..C-2."""
+def fcos_detect(conf, reg, center, score_thr, max_boxes, iou_thr, **nms):
+    """FCOS.py:197-265.  conf / reg / center: the five level tensors [H, W, C | 4 | 1] of one image; classes 0..C-2.  nms: method / sigma / min_score of
+    `_per_class_nms`."""
     pconf, pbbox = ops.fcos_decode_candidates(conf, reg, center)
     cand = (pconf >= score_thr).to(torch.uint8)
-    return _per_class_nms(pconf, pbbox, cand, pconf.shape[1] - 1, max_boxes, iou_thr)
+    return _per_class_nms(pconf, pbbox, cand, pconf.shape[1] - 1, max_boxes, iou_thr, **nms)
 
 
-def yolov2_detect(pred0, priors_flat, score_thr, max_boxes, iou_thr, stride=32.0):
-    """YOLOv2.py:177-201.  pred0: [H, W, P, C + 5] of one image."""
+def yolov2_detect(pred0, priors_flat, score_thr, max_boxes, iou_thr, stride=32.0, **nms):
+    """YOLOv2.py:177-201.  pred0: [H, W, P, C + 5] of one image.  nms: method / sigma / min_score of `_per_class_nms`."""
     conf, bbox = ops.yolov2_decode_candidates(pred0, priors_flat, stride)
     cand = (conf >= score_thr).to(torch.uint8)
-    return _per_class_nms(conf, bbox, cand, conf.shape[1], max_boxes, iou_thr)
+    return _per_class_nms(conf, bbox, cand, conf.shape[1], max_boxes, iou_thr, **nms)
 
 
 class YOLOv2Loss:

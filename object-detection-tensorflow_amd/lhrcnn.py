@@ -357,7 +357,8 @@ class LHRCNN(RefineDet320):
         ops.crop_and_resize_fwd(f.t, f.ld, 1, f.H, f.W, f.C, st.roi_box, st.roi_img, CROP, st.roi, st.ldr)
         self._dense_fwd(st)
         ops.lhrcnn_rcnn_decode(st.logits32, st.ldl, st.pbbox32, st.ldb, st.roi_prop, st.roi_img, self.num_classes, self.nms_score_threshold, st.conf, st.boxes, st.cand)
-        scores, bbox, cid = heads._per_class_nms(st.conf, st.boxes, st.cand, self.num_classes - 1, self.nms_max_boxes, self.nms_iou_threshold)
+        scores, bbox, cid = heads._per_class_nms(st.conf, st.boxes, st.cand, self.num_classes - 1, self.nms_max_boxes, self.nms_iou_threshold,
+                                                 **self._nms_params())
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     # ------------------------------------------------------------------ the reference's variable names

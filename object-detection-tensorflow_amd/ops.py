@@ -490,6 +490,25 @@ def nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, sc
          valid_estride, valid_value, n, _p(n_dev), N, num_classes, int(max_out), float(iou_thr), _p(out_idx), cap, _p(out_cnt), _stream())
 
 
+NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}        # config['nms_method'] -> the `method` of odtk_soft_nms_image_class
+
+
+def soft_nms_image_class(boxes, box_istride, scores, score_istride, score_cstride, score_estride, valid, valid_istride, valid_cstride, valid_estride,
+                         valid_value, n, n_dev, N, num_classes, max_out, method, iou_thr, sigma, min_score, out_idx, out_score, cap, out_cnt):
+    """soft-NMS of N * num_classes problems (image x class) in one launch: `method` 0 hard, 1 linear, 2 gaussian (NMS_METHODS); the picks to out_idx, their
+    decayed scores to out_score [N, num_classes, cap]; operand addressing as in include/odtk.h"""
+    call("odtk_soft_nms_image_class", _p(boxes), box_istride, _p(scores), score_istride, score_cstride, score_estride, _p(valid), valid_istride,
+         valid_cstride, valid_estride, valid_value, n, _p(n_dev), N, num_classes, int(max_out), int(method), float(iou_thr), float(sigma), float(min_score),
+         _p(out_idx), _p(out_score), cap, _p(out_cnt), _stream())
+
+
+def detection_pack_scored(nms_idx, nms_cnt, nms_score, conf, boxes, counts, offsets, scores, bbox, class_id):
+    """detection_pack with the scores taken from the soft-NMS table nms_score [N, nc, cap] instead of conf"""
+    N, nc, cap = nms_idx.shape
+    call("odtk_detection_pack_scored", _p(nms_idx), _p(nms_cnt), _p(nms_score), N, nc, cap, _p(conf), conf.shape[1] * conf.shape[2], conf.shape[2],
+         _p(boxes), boxes.shape[1] * 4, _p(counts), _p(offsets), _p(scores), _p(bbox), _p(class_id), _stream())
+
+
 def compact_rows(cand, num_classes, cap_rows, rows, counts):
     """cand [N, A, ld] u8 -> rows [N, cap_rows] int32 (ascending indices of the rows with a candidate among the first num_classes columns), counts [N]"""
     N, A, ld = cand.shape

@@ -469,7 +469,7 @@ class RefineDet320(heads.BatchedInference, F32Warmup, graph.OwnedGradients, Dete
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
 
     def _make_tail(self):
-        return heads.BatchedTail(self.batch_size, self.A, self.num_classes - 1, self.nms_max_boxes, self.dev)
+        return heads.BatchedTail(self.batch_size, self.A, self.num_classes - 1, self.nms_max_boxes, self.dev, **self._nms_params())
 
     def _launch_tail(self, t):
         ops.refinedet_decode_batched(self.arm_loc, self.arm_conf, self.odm_loc, self.odm_conf, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf,

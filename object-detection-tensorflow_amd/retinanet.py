@@ -307,7 +307,7 @@ class RetinaNet(heads.BatchedInference, graph.SharedGradients, DetectorBase):
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
 
     def _make_tail(self):
-        return heads.BatchedTail(self.batch_size, self.pconf.shape[1], self.num_classes - 1, self.nms_max_boxes, self.dev)
+        return heads.BatchedTail(self.batch_size, self.pconf.shape[1], self.num_classes - 1, self.nms_max_boxes, self.dev, **self._nms_params())
 
     def _launch_tail(self, t):
         ops.retina_decode_batched(self.pconf, self.pbox, self.anc[2], self.anc[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)

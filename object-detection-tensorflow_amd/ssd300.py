@@ -184,6 +184,7 @@ class SSD300(BatchedInference, F32Warmup, DetectorBase):
         self.nms_score_threshold = config['nms_score_threshold']
         self.nms_max_boxes = config['nms_max_boxes']
         self.nms_iou_threshold = config['nms_iou_threshold']
+        self._read_nms_method(config, True)
         self.pretraining_weight = config['pretraining_weight']
         assert self.num_classes + 4 == 25 or True
         self.row = self.num_classes + 4
@@ -1149,7 +1150,7 @@ class SSD300(BatchedInference, F32Warmup, DetectorBase):
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))
 
     def _make_tail(self):
-        return BatchedTail(self.batch_size, self.NUM_PRIORS, self.num_classes - 1, self.nms_max_boxes, self.dev)
+        return BatchedTail(self.batch_size, self.NUM_PRIORS, self.num_classes - 1, self.nms_max_boxes, self.dev, **self._nms_params())
 
     def _launch_tail(self, t):
         ops.ssd_decode_batched(self.pred, self.num_classes, self.pri[2], self.pri[3], self.nms_score_threshold, t.conf, t.boxes, t.keep, t.cand)

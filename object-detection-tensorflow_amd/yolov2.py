@@ -135,7 +135,7 @@ class YOLOv2(RefineDet320):
         self._forward(False, subtract_mean=bool(self.config.get('test_subtract_mean', False)))      # reference quirk: the fed tensor is `images - mean`
         H, W = self.grid
         scores, bbox, cid = heads.yolov2_detect(self.pred[0].view(H, W, self.num_priors, self.num_classes + 5), self.priors_flat,
-                                                self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold, STRIDE)
+                                                self.nms_score_threshold, self.nms_max_boxes, self.nms_iou_threshold, STRIDE, **self._nms_params())
         return [scores.cpu().numpy(), bbox.cpu().numpy().reshape(-1, 4), cid.cpu().numpy()]
 
     def load_pretraining_weight(self, path):

@@ -225,7 +225,7 @@ class YOLOv3(heads.BatchedInference, F32Warmup, graph.SharedGradients, DetectorB
 
     def _make_tail(self):
         L = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in self.preds)
-        return heads.BatchedTail(self.batch_size, L, self.num_classes, self.nms_max_boxes, self.dev, bool_cand=True)
+        return heads.BatchedTail(self.batch_size, L, self.num_classes, self.nms_max_boxes, self.dev, bool_cand=True, **self._nms_params())
 
     def _launch_tail(self, t):
         """The decode is a LOOP of the existing launch, odtk_yolov3_decode_candidates, one per image slot into [N, L, C] / [N, L, 4]: that entry point takes the

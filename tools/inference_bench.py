@@ -10,7 +10,10 @@ Per class and engine (--classes ssd300,ssd512,yolov3,retinanet,centernet,refined
     read-back (wall clock); CenterNet's tail is the decode alone (score / arg-max + one top-k workgroup per image, heads.CenterNetBatched).
 Only pairs measured in the same process count: two boxes of a pool differ by more than most changes.  Synthetic weights and pixels; the score threshold is
 lowered for the SSD family (--score-threshold, default 0.01) so that the tail has detections to carry; the other classes keep their configuration's
-threshold (at 0.01 a random-weight RetinaNet has more candidate rows than the NMS takes)."""
+threshold (at 0.01 a random-weight RetinaNet has more candidate rows than the NMS takes).
+--nms-methods hard,linear,gaussian: only the tail, once per method, on ONE decode output: a model at the largest B runs one batch, then a BatchedTail per
+method is timed by HIP events on that model's conf / boxes / cand (NMS + pack; 'hard' is the launch chain of odtk_nms_image_class + odtk_detection_pack, the
+soft methods odtk_soft_nms_image_class + odtk_detection_pack_scored), with the detections each returns."""
 import argparse
 import json
 import os
@@ -134,6 +137,26 @@ def tail_times(m, name, reps):
     return out
 
 
+def tail_by_method(name, engine, a):
+    """the NMS + pack time of the batched tail per nms_method at the largest B, on the decode output of one batch of synthetic pictures"""
+    from odtk import heads
+    B = [b for b in BATCHES[name] if b <= a.max_batch][-1]
+    thr = a.score_threshold if a.score_threshold is not None else (0.01 if name in ('ssd300', 'ssd512') else None)
+    m, size = build(name, engine, B, thr)
+    g = torch.Generator().manual_seed(11)
+    m.test_images((torch.rand(B, size, size, 3, generator=g) * 255).round().numpy())
+    t = m._tail_batched
+    cand = t.cand.view(torch.uint8)
+    row = {'class': name, 'engine': engine, 'input': size, 'N': t.N, 'rows_per_image': t.A, 'classes': t.nc, 'max_boxes': t.max_boxes,
+           'score_threshold': m.nms_score_threshold, 'candidates_per_problem_mean': float(cand.sum()) / (t.N * t.nc),
+           'candidates_per_problem_max': int(cand.sum(dim=1).max()), 'nms_pack_ms': {}, 'detections': {}}
+    for method in a.nms_methods.split(','):
+        t2 = heads.BatchedTail(t.N, t.A, t.nc, t.max_boxes, t.dev, method=method, sigma=m.soft_nms_sigma, min_score=m.soft_nms_min_score)
+        row['nms_pack_ms'][method] = events_ms(lambda: t2.launch(t.conf, t.boxes, cand, m.nms_iou_threshold), max(a.reps, 20))
+        row['detections'][method] = sum(len(d[0]) for d in t2.read())
+    return row
+
+
 def run(name, engine, a):
     Bs = [b for b in BATCHES[name] if b <= a.max_batch]
     thr = a.score_threshold if a.score_threshold is not None else (0.01 if name in ('ssd300', 'ssd512') else None)
@@ -181,12 +204,13 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--max-batch', type=int, default=32)
     ap.add_argument('--score-threshold', type=float, default=None, help='default: 0.01 for the SSD family, the class configuration otherwise')
+    ap.add_argument('--nms-methods', default=None, help="comma list of 'hard', 'linear', 'gaussian': time only the tail (NMS + pack), once per method")
     a = ap.parse_args()
     torch.set_num_threads(16)
     rows = []
     for name in a.classes.split(','):
         for engine in (a.engines.split(',') if a.engines else ENGINES[name]):
-            rows.append(run(name, engine, a))
+            rows.append(tail_by_method(name, engine, a) if a.nms_methods else run(name, engine, a))
             print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
             torch.cuda.empty_cache()
     print(json.dumps({'tool': 'inference_bench', 'device': torch.cuda.get_device_name(0), 'rows': rows}))
